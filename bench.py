@@ -1,22 +1,33 @@
 """Benchmark: U-Net training images/s at 512x512x1, batch 8 per GPU, fp32
 (BASELINE.json configs[1]; weak scaling over 1/2/4/8 MI355X with an RCCL
-gradient all-reduce over xGMI).  The same invocation also times the bf16-operand
-GEMM plan (configs[2] per GPU: global batch 8 x N) and reports it as the
-``bf16`` sub-object; ``--dtype`` picks the precision of the headline ``value``
-(default fp32 = configs[1]); ``--channels 3 --size 572`` is the configs[4]
-stress shape.
+gradient all-reduce over xGMI).  With ``--full`` the same invocation also times
+the bf16-operand GEMM plan (configs[2] per GPU: global batch 8 x N) and reports
+it as the ``bf16`` sub-object; ``--dtype`` picks the precision of the headline
+``value`` (default fp32 = configs[1]); ``--channels 3 --size 572`` is the
+configs[4] stress shape.
 
 A step = forward + WeightedCrossEntropyLoss + backward + all-reduce (N>1) +
 SGD(momentum 0.99) over one synthetic batch resident in HBM, exactly the body
 of scripts/train.py:108-131 (no per-step .item()).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
-Prints ONE compact JSON line on rank 0 (the contract fields and every headline
-number, ~1.5 KB so a 2 KB log tail holds all of it) and writes the full record
--- per-launch-site timings, kernel classes, descriptions -- to --detail-out
-(default gpurun_out/bench_detail.json).  The full record carries:
+A plain run does only what the headline figure needs: it builds the model,
+runs W warm-up steps, times K steps of the --dtype precision and prints ONE
+compact JSON line on rank 0 (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...).  ``--dump-outputs DIR`` also writes what the last timed step
+computed (loss, logits, and a seeded sample of the updated
+parameters, the BatchNorm running statistics) as DIR/<name>.npy; model, batch
+and sample indices are seeded and the headline leg runs in the library's
+deterministic mode (no fp32 atomics; ``--no-deterministic`` for the default
+kernels), so two runs with the same arguments write identical arrays and two
+builds can be compared array for array.
+
+``--full`` adds every other leg (each --no-* / --extra-dtypes switch below
+trims it): the line then carries every headline number (~1.5 KB so a 2 KB log
+tail holds all of it) and the full record -- per-launch-site timings, kernel
+classes, descriptions -- is written to --detail-out.  The full record carries:
 * roofline: the implicit-GEMM conv family (63 GEMM launch sites per step) at
   the MFMA peak of the precision, HIP-event timed on the plan's stream in an
   extra untimed step; `achieved` counts the MFMA flops the chosen variants
@@ -195,15 +206,17 @@ def compact_line(out, detail):
     line["data"] = "synthetic x~U[0,1), Bernoulli(0.4) targets, 10+1/freq weights, kaiming init"
     line["config"] = {"workload": out["config"]["workload"].split(":")[0] + " (fwd+WCE+bwd+SGD)",
                       **pick(out["config"], ("global_batch", "image", "parallelism"))}
-    rl = out["roofline"]
-    line["roofline"] = {**pick(rl, ("bound", "achieved", "peak", "unit", "frac", "frac_measured", "traffic")),
-                        "kernel": "conv GEMM family (executed MFMA flops)"}
+    if "roofline" in out:  # --full: the per-kernel timing step ran
+        rl = out["roofline"]
+        line["roofline"] = {**pick(rl, ("bound", "achieved", "peak", "unit", "frac", "frac_measured", "traffic")),
+                            "kernel": "conv GEMM family (executed MFMA flops)"}
     if "cpu_baseline" in out:
         cb = out["cpu_baseline"]
         line["cpu_baseline"] = {**pick(cb, ("value", "unit", "cores", "kind", "batch1_value")),
                                 "sample": "torch-CPU restatement of the reference step, batch 8 / 1, median of 5"}
-    line["bottleneck"] = pick(out.get("bottleneck"), ("ms", "frac", "frac_measured"))
-    line["stage1"] = pick(out.get("stage1"), ("ms", "achieved_gbs", "frac"))
+    if "roofline" in out:
+        line["bottleneck"] = pick(out.get("bottleneck"), ("ms", "frac", "frac_measured"))
+        line["stage1"] = pick(out.get("stage1"), ("ms", "achieved_gbs", "frac"))
     for d in ("fp32", "bf16", "bf16x3"):
         if d in out and isinstance(out[d], dict) and "value" in out[d]:
             r = out[d]
@@ -224,7 +237,9 @@ def compact_line(out, detail):
         line["comm"] = pick(out["comm"], ("dtype", "bytes_per_step"))
     if out.get("peaks_measured"):
         line["peaks"] = pick(out["peaks_measured"], ("bf16_mfma_tflops", "fp32_mfma_tflops", "hbm_gbs"))
-    line["lib"] = pick(out.get("lib"), ("lib_src", "src_match", "tune_db_entries"))
+    line["lib"] = pick(out.get("lib"), ("lib_src", "src_match", "tune_db_entries", "deterministic"))
+    if out.get("outputs"):
+        line["outputs"] = pick(out["outputs"], ("dir", "arrays"))
     if detail:
         line["detail"] = detail
     return line
@@ -325,6 +340,44 @@ def run_farm(args, dtype, device, iters=20, warmup=3):
                        "mask_shape": list(mask.shape)}}
 
 
+DUMP_SAMPLE = 1 << 22  # elements kept of an array larger than this (16 MiB of float32)
+
+
+def dump_outputs(path, trainer, loss):
+    """--dump-outputs: what the last timed step left a caller of Trainer.step
+    -- the loss it returned, the logits it computed, the parameters (flat
+    buffer, state_dict order) and BatchNorm running statistics it updated -- as
+    float32 <path>/<name>.npy.  An array of more than DUMP_SAMPLE elements is
+    written as the DUMP_SAMPLE elements at sorted indices drawn once from a
+    generator seeded with its length (the same elements in every run of every
+    build; at the default shape 6.7 MB of logits + 16.8 MB of parameters).
+    The headline leg runs in the library's deterministic mode (main()), so two
+    runs of one build with the same arguments write identical arrays -- where
+    the tuning database holds the shapes' choices (profiles/tune_db.txt: the
+    default 8 x 512^2 x 1 workload in fp32 and bf16, 8 x 572^2 x 3 in bf16).
+    Any other shape is tuned live by timing, and two runs may then pick
+    different kernels and differ in rounding; --tune-db-out of one run and
+    --tune-db in the next replays the first run's choices."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    bufs = trainer.flat_buffers.flat
+    arrays = {"loss": loss, "logits": trainer.logits, "params": trainer.flat.flat}
+    if bufs is not None:
+        arrays["bn_running_stats"] = bufs
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(t.numel())
+            idx = torch.randperm(t.numel(), generator=g)[:DUMP_SAMPLE].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return {"dir": path, "arrays": written, "step": "the last timed step"}
+
+
 def run_precision(args, dtype, device, pg, world, rank):
     """Time args.steps train steps of one GEMM precision; returns its summary.
     UNET_MAIN_PRIORITY=<p> (experiment): the whole leg runs on a torch stream
@@ -384,6 +437,22 @@ def _run_precision(args, dtype, device, pg, world, rank):
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed, median_ms = float(e[0].item()), float(e[1].item())
     final_loss = float(loss.item())
+    outputs = dump_outputs(args.dump_outputs, trainer, loss) if args.dump_outputs and rank == 0 else None
+    head = {
+        # BASELINE.md: images/s = world * batch / median step time
+        "value": round(world * args.batch / (median_ms * 1e-3), 3),
+        "ms_per_step": round(median_ms, 3),
+        "mean_ms_per_step": round(1e3 * elapsed / args.steps, 3),
+        "wall_value": round(world * args.batch * args.steps / elapsed, 3),
+        "step_ms_range": [round(step_ms[0], 3), round(step_ms[-1], 3)],
+        "dtype": dtype,
+        "final_loss": round(final_loss, 5),
+        "outputs": outputs,
+    }
+    if not args.full:  # a plain run: the headline figure only
+        head["comm"] = None if pg is None else {"dtype": str(trainer.comm_dtype).replace("torch.", ""),
+                                                "bytes_per_step": trainer.reducer.bytes_per_step}
+        return head
 
     # per-kernel-class timing of one extra (untimed) step: HIP events recorded by
     # the plan on the stream its kernels run on
@@ -423,15 +492,8 @@ def _run_precision(args, dtype, device, pg, world, rank):
                    "mfma_tflops": round(xfl[k] / (v[0] * 1e-3) / 1e12, 2) if v[0] > 0 and xfl[k] else None,
                    "gbs": round(v[2] / (v[0] * 1e-3) / 1e9, 1) if v[0] > 0 and v[2] else None}
                for k, v in tim.items()}
-    imgs = world * args.batch * args.steps
     return {
-        # BASELINE.md: images/s = world * batch / median step time
-        "value": round(world * args.batch / (median_ms * 1e-3), 3),
-        "ms_per_step": round(median_ms, 3),
-        "mean_ms_per_step": round(1e3 * elapsed / args.steps, 3),
-        "wall_value": round(imgs / elapsed, 3),
-        "step_ms_range": [round(step_ms[0], 3), round(step_ms[-1], 3)],
-        "dtype": dtype,
+        **head,
         "roofline": {"bound": "mfma", "kernel": f"implicit-GEMM conv family (fwd/dgrad igemm + wgrad, {dtype} operands)",
                      "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
                      "frac": round(achieved / peak, 4),
@@ -478,7 +540,6 @@ def _run_precision(args, dtype, device, pg, world, rank):
                    "frac_measured": round(st[2] / (st[0] * 1e-3) / 1e9 / HBM_MEASURED_GBS, 4) if st[0] > 0 else None,
                    "traffic": fam.get("stage1", {}).get("bytes_per_step")},
         "kernels": kernels,
-        "final_loss": round(final_loss, 5),
         "comm": comm,
     }
 
@@ -494,6 +555,16 @@ def main():
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16x3"],
                     help="GEMM arithmetic of the headline value: fp32 MFMA; bf16 = bf16-in / fp32-acc MFMA; "
                          "bf16x3 = fp32-accurate split operands (hi*hi + hi*lo + lo*hi on the bf16 MFMA)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (loss, logits, a sample of the "
+                         "updated parameters, BatchNorm statistics) as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure: the per-kernel timing step (roofline, "
+                         "bottleneck, stage 1), --extra-dtypes, c5 and farm, IoU, CPU baseline, peak probes, and "
+                         "write --detail-out; the switches below trim what --full runs")
+    ap.add_argument("--no-deterministic", action="store_true",
+                    help="run the headline leg with the library's default weight-gradient variants (fp32 atomics: "
+                         "runs then differ in the last bits of every step) instead of its deterministic mode")
     ap.add_argument("--extra-dtypes", default="bf16",
                     help="comma-separated precisions also timed in this invocation and reported as sub-objects "
                          "('' = none; profiling runs use '')")
@@ -517,6 +588,9 @@ def main():
     ap.add_argument("--full-stdout", action="store_true", help="print the full record instead of the compact line "
                     "(tools that read kernel classes from stdout)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: warm up, time the steps of --dtype, print the line
+        args.extra_dtypes, args.detail_out = "", ""
+        args.no_extras = args.no_iou = args.no_cpu_baseline = args.no_peaks = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -543,7 +617,20 @@ def main():
         if tune_db_entries < 0:
             raise RuntimeError(f"unet_tuning_load({args.tune_db}) failed: {tune_db_entries}")
 
+    # The headline leg runs in the library's deterministic mode (every weight
+    # gradient on an atomic-free variant, its choices replayed from --tune-db):
+    # with the seeded inputs, two runs compute bit-identical steps, so what
+    # --dump-outputs writes can be compared between runs and builds.  The fp32
+    # atomics of the default mode differ in the last bits per step, which 25
+    # SGD steps amplify to ~5e-3 on the logits.  Measured cost: 25.75 against
+    # 25.60 ms per fp32 step.  The other legs of --full keep the default mode.
+    det_default = int(os.environ.get("UNET_DETERMINISTIC", "0") or 0) != 0
+    if not args.no_deterministic:
+        _ulib.check(lib.unet_set_tuning(b"deterministic", 1), "unet_set_tuning(deterministic)")
     main_res = run_precision(args, args.dtype, device, pg, world, rank)
+    if not args.no_deterministic:
+        lib.unet_set_tuning(b"deterministic", int(det_default))
+    args.dump_outputs = None  # the outputs written are the headline leg's
     extras = {}
     for d in [d for d in args.extra_dtypes.split(",") if d and d != args.dtype]:
         extras[d] = run_precision(args, d, device, pg, world, rank)
@@ -580,10 +667,11 @@ def main():
                        "parallelism": f"dp{world}"},
         }
         for k in ("mean_ms_per_step", "wall_value", "step_ms_range", "roofline", "bottleneck", "stage1", "kernels",
-                  "gemm_sites", "final_loss"):
-            out[k] = main_res[k]
+                  "gemm_sites", "final_loss", "outputs"):
+            if main_res.get(k) is not None:  # a plain run has no per-kernel timing step
+                out[k] = main_res[k]
         out["lib"] = {**ident, "tune_db": os.path.relpath(args.tune_db, ROOT) if tune_db_entries > 0 else None,
-                      "tune_db_entries": tune_db_entries}
+                      "tune_db_entries": tune_db_entries, "deterministic": not args.no_deterministic}
         if main_res["comm"] is not None:
             out["comm"] = main_res["comm"]
         for d, r in extras.items():

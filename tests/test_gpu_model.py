@@ -714,6 +714,44 @@ def test_trainer_bench_plan_batch8_512_vs_reference_and_autograd(bench_tuning):
     print(f"batch-8 512^2 Trainer step: {low} low-margin pixels")
 
 
+def test_trainer_bench_deterministic_plan_batch8_512_vs_reference(bench_tuning):
+    """The kernel mix bench.py's headline leg times: the same workload in the
+    library's deterministic mode, its weight-gradient variants replayed from
+    the `det` keys of profiles/tune_db.txt (no shape tuned live, no site left
+    on fp32 atomics).  Same reference run and the same bars as the default mix
+    above; the keys are per shape, so 8 x 512^2 is the only size that replays
+    them."""
+    from unet_amd import _lib
+    from unet_amd.train import Trainer
+    lib = _lib.load()
+    z = np.load(os.path.join(G, "train_n8_512.npz"), allow_pickle=False)
+    seed, n, h = int(z["x_seed"]), int(z["n"]), int(z["h"])
+    params = O.hash_init(1, 2, seed=seed, bn_random=True)
+    xd, td, wd = (torch.from_numpy(a).cuda() for a in F.make_inputs(seed, n, 1, h))
+    before = set(_lib.tuning_report().splitlines())
+    _lib.check(lib.unet_set_tuning(b"deterministic", 1), "unet_set_tuning")
+    try:
+        lib.unet_nondeterministic_sites(1)
+        b = make_model(params)
+        tr = Trainer(b, n, h, h, lr=1e-4, momentum=0.99)
+        lb = tr.forward_loss(xd, td, wd)
+        tr.backward_and_reduce(xd)
+        torch.cuda.synchronize()
+        assert lib.unet_nondeterministic_sites(0) == 0
+    finally:
+        lib.unet_set_tuning(b"deterministic", 0)
+    live = [ln for ln in set(_lib.tuning_report().splitlines()) - before if ln and "tuning db" not in ln]
+    if bench_tuning:  # (UNET_TEST_TUNE_DB='' tunes live on purpose)
+        assert not live, live  # every choice came from the database
+    lg = tr.logits.double().cpu().numpy()
+    check_full_size_outputs(lg, lb.item(), z, lg.shape[-1])
+    check_grad_digests(list(zip([k for k, _ in b.named_parameters()], tr.flat.grad_views)), z)
+    sd = b.state_dict()
+    for k in z.files:
+        if k.startswith("buf/"):
+            np.testing.assert_allclose(sd[k[4:]].cpu().numpy(), z[k], rtol=1e-4, atol=1e-5, err_msg=k)
+
+
 @pytest.mark.parametrize("defer", [False, True])
 def test_segmented_backward_matches_whole_backward(defer):
     """The data-parallel backward schedule (plan.backward(s, s+1) for the 9

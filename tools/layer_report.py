@@ -1,4 +1,4 @@
-"""Per-layer report from a rocprofv3 kernel trace of bench.py.
+"""Per-layer report from a rocprofv3 kernel trace of `bench.py --full`.
 
 Maps the k_igemm / k_wgrad dispatches of one training step onto the U-Net
 layers (the plan's fixed launch order) and prints time and TFLOP/s per layer.
@@ -55,7 +55,7 @@ def main():
     h = int(sys.argv[3]) if len(sys.argv) > 3 else 512
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"]))
     starts = [i for i, r in enumerate(rows) if "conv_first_fwd" in r["Kernel_Name"]]
-    # the last step of bench.py is its serial timing step (no side stream)
+    # the last step of `bench.py --full` is its serial timing step (no side stream)
     step = rows[starts[-1]:]
     conv = [r for r in step if any(k in r["Kernel_Name"] for k in ("k_igemm", "k_wgrad", "k_conv3"))]
     seq = geometry(n, h)

@@ -3,7 +3,7 @@
 # per MFMA, LDS bank conflicts) of any python command, reduced per kernel by
 # tools/pmc_kernels.py.  Each pass under its own time limit.
 #   tools/prof_mix.sh <outdir> <script.py> [args...]
-#   e.g. tools/prof_mix.sh gpurun_out/mix bench.py --no-cpu-baseline --no-iou --extra-dtypes= --no-extras --steps 2 --warmup 1
+#   e.g. tools/prof_mix.sh OUT/mix bench.py --full --no-deterministic --no-cpu-baseline --no-iou --extra-dtypes= --no-extras --steps 2 --warmup 1
 set -o pipefail
 out=$1; shift
 export TMPDIR=/tmp

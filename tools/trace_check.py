@@ -1,7 +1,7 @@
 """Per-step kernel times of a `rocprofv3 --kernel-trace` run of bench.py.
 
-    rocprofv3 --kernel-trace --stats -d gpurun_out/tr -o run -- python bench.py --steps K --warmup W
-    python tools/trace_check.py gpurun_out/tr W K [bench.json]
+    rocprofv3 --kernel-trace --stats -d OUT/tr -o run -- python bench.py --full --no-deterministic --full-stdout --steps K --warmup W > bench.json
+    python tools/trace_check.py OUT/tr W K [bench.json]
 
 `rocprofv3 --stats` averages each kernel over every dispatch of the process,
 autotuner trials included (the tuner times each candidate tile in the first

@@ -304,7 +304,19 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm_ring(const IgemmArgs a
 
 // ---------------------------------------------------------------------------
 // tile ids (igemm.hip tile_info 91-99)
+//
+// The nine tiles' kernels compile in three translation units of three tiles
+// each: this file and gemm_ring_p1.hip / gemm_ring_p2.hip, which include it
+// with GEMM_RING_PART set (as one unit they took a third of a from-scratch
+// build's wall time).  Part 0 holds the shape tables and the dispatch.
 // ---------------------------------------------------------------------------
+#ifndef GEMM_RING_PART
+#define GEMM_RING_PART 0
+#endif
+hipError_t go_gemm_ring_p1(const IgemmArgs& a, hipStream_t s, int tile);  // tiles 94-96
+hipError_t go_gemm_ring_p2(const IgemmArgs& a, hipStream_t s, int tile);  // tiles 97-99
+
+#if GEMM_RING_PART == 0
 bool gemm_ring_tile_shape(int tile, int& bm, int& bn) {
   switch (tile) {
     case 91: bm = 128; bn = 128; return true;  // 4 waves (2 x 2), BK 64, 4 stages: 128 KB
@@ -334,6 +346,7 @@ bool gemm_ring_fits(const IgemmArgs& a, int tile) {
          g.Cg <= 2048 && a.N % bn == 0 && a.batch <= 1 && bytes < 4294967296.0 &&
          (double)a.N * a.K * 2 < 4294967296.0;
 }
+#endif  // GEMM_RING_PART == 0
 
 template <int BM, int BN, int WM, int WN, int BK, int NSTG>
 static hipError_t go_gemm_ring(const IgemmArgs& a, hipStream_t s) {
@@ -361,19 +374,33 @@ static hipError_t go_gemm_ring(const IgemmArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+#if GEMM_RING_PART == 0
 hipError_t go_gemm_ring_tile(const IgemmArgs& a, hipStream_t s, int tile) {
   if (!gemm_ring_fits(a, tile)) return hipErrorInvalidValue;
   switch (tile) {
     case 91: return go_gemm_ring<128, 128, 2, 2, 64, 4>(a, s);
     case 92: return go_gemm_ring<256, 128, 4, 2, 64, 3>(a, s);
     case 93: return go_gemm_ring<128, 256, 2, 4, 64, 3>(a, s);
+    case 94: case 95: case 96: return go_gemm_ring_p1(a, s, tile);
+    default: return go_gemm_ring_p2(a, s, tile);
+  }
+}
+#elif GEMM_RING_PART == 1
+hipError_t go_gemm_ring_p1(const IgemmArgs& a, hipStream_t s, int tile) {
+  switch (tile) {
     case 94: return go_gemm_ring<128, 128, 2, 4, 64, 4>(a, s);
     case 95: return go_gemm_ring<64, 128, 1, 4, 64, 4>(a, s);
-    case 96: return go_gemm_ring<256, 256, 2, 4, 32, 4>(a, s);
+    default: return go_gemm_ring<256, 256, 2, 4, 32, 4>(a, s);
+  }
+}
+#else
+hipError_t go_gemm_ring_p2(const IgemmArgs& a, hipStream_t s, int tile) {
+  switch (tile) {
     case 97: return go_gemm_ring<256, 128, 4, 2, 32, 6>(a, s);
     case 98: return go_gemm_ring<128, 256, 2, 4, 32, 6>(a, s);
     default: return go_gemm_ring<128, 128, 2, 2, 32, 8>(a, s);
   }
 }
+#endif
 
 }  // namespace unet
