@@ -165,7 +165,8 @@ def test_host_sanitizer_selftest():
     exe = os.path.join(os.path.dirname(__file__), "..", "build", "asan", "host_selftest")
     if not os.path.exists(exe):
         pytest.skip("host_selftest not built (make -C unet-segmentation_amd/csrc sanitize)")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300,
+    golden = os.path.join(os.path.dirname(__file__), "golden", "gemm_selection.txt")  # the GEMM variant selection
+    r = subprocess.run([exe, golden], capture_output=True, text=True, timeout=300,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1"))
     assert r.returncode == 0, r.stdout + r.stderr
     assert "all checks passed" in r.stdout

@@ -5,16 +5,21 @@
 // segment table, argument validation of the C ABI, the linear sum assignment
 // (random, tied, rectangular, degenerate matrices; checked for a valid
 // assignment and against brute force on small ones), the tracker's host step
-// on a synthetic sequence, the tuning report.
+// on a synthetic sequence, the tuning report, and the GEMM variant selection
+// (tile tables, fits, candidate lists, forced knobs) over synthetic launch
+// arguments, compared line for line with tests/golden/gemm_selection.txt.
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "../include/unet_hip.h"
+#include "unet_internal.h"
 
 static int fails = 0;
 #define CHECK(c)                                                   \
@@ -155,11 +160,268 @@ static void test_misc() {
   CHECK(unet_set_tuning("no_such_key", 1) != 0);
 }
 
-int main() {
+// ---------------------------------------------------------------------------
+// GEMM variant selection.  One record per synthetic launch: the tuning key, the
+// heuristic tile, every table tile's fits / workgroup count / slots, the ordered
+// candidate list, and what the forced knobs resolve to.  The golden file holds
+// each record's key and a 64-bit FNV-1a hash of the whole record; it was
+// recorded before the tile tables replaced the per-id switches, so any differing
+// line means the selection changed (the full record is then printed).  No GPU
+// call is made (num_cus() is 256 without a device).
+// ---------------------------------------------------------------------------
+namespace unet {
+extern int g_tune_igemm, g_tune_wgrad;
+}
+static float g_dummy[4];
+
+static void appendf(std::string& o, const char* fmt, ...) {
+  char b[512];
+  va_list ap;
+  va_start(ap, fmt);
+  std::vsnprintf(b, sizeof b, fmt, ap);
+  va_end(ap);
+  o += b;
+}
+
+static unet::Src mk_src(int hw, int c, int h16, bool tf) {
+  unet::Src s;
+  s.ptr = g_dummy;
+  s.H = s.W = hw;
+  s.C = c;
+  s.h16 = h16;
+  if (tf) s.scale = s.shift = g_dummy;
+  return s;
+}
+
+// kind 0: 3x3 stride 1, one source; 1: two sources (c_split = Cg / 2);
+// 2: convT forward (1x1 taps, pixel shuffle); 3: convT input gradient (2x2 stride 2)
+static unet::IgemmArgs mk_igemm(int kind, int Cg, int N, int hw, int nimg, int h16, bool tf, int fwd, int prec) {
+  using namespace unet;
+  IgemmArgs a;
+  Gather& g = a.a;
+  g.Cg = Cg;
+  g.c_split = kind == 1 ? Cg / 2 : Cg;
+  g.Hg = g.Wg = hw;
+  g.nimg = nimg;
+  if (kind <= 1) {
+    g.taps_h = g.taps_w = 3;
+    const int cs = kind == 1 ? Cg / 2 : Cg;
+    g.s[0] = mk_src(hw + 2, cs, h16, tf);
+    g.s[1] = kind == 1 ? mk_src(hw + 2, cs, h16, false) : g.s[0];
+  } else if (kind == 2) {
+    g.s[0] = g.s[1] = mk_src(hw, Cg, h16, tf);
+    a.e.shuffle_co = N / 4;
+  } else {
+    g.taps_h = g.taps_w = 2;
+    g.stride = 2;
+    g.s[0] = g.s[1] = mk_src(2 * hw, Cg, h16, false);
+  }
+  a.M = nimg * hw * hw;
+  a.N = N;
+  a.K = g.taps_h * g.taps_w * Cg;
+  static uint16_t w16[4];
+  if (prec == 0) a.b = g_dummy;
+  else a.bh = w16;
+  if (prec == 2) a.bl = w16;
+  a.e.d[0] = Dst{g_dummy, kind == 2 ? 2 * hw : hw, kind == 2 ? 2 * hw : hw, kind == 2 ? N / 4 : N, 0, 0, 0};
+  a.fwd = kind <= 1 ? fwd : 0;
+  static double st[4];
+  if (a.fwd) a.e.stats = st;
+  a.slab = g_dummy;
+  if (prec == 0) {
+    a.wino_ws = g_dummy;
+    a.wino_ws_bytes = (size_t)1 << 31;
+  }
+  return a;
+}
+
+// kind 0 / 1: 3x3 weight gradient (one / two X sources); 2: convT weight gradient
+static unet::WgradArgs mk_wgrad(int kind, int Co, int Ci, int hw, int nimg, int h16, bool tf, int prec, bool slab,
+                                int accumulate, int batch) {
+  using namespace unet;
+  WgradArgs a{};
+  Gather& ga = a.ga;
+  Gather& gb = a.gb;
+  ga.Hg = ga.Wg = gb.Hg = gb.Wg = hw;
+  ga.nimg = gb.nimg = nimg;
+  if (kind <= 1) {  // ga: padded dY (pad 2), gb: X with 3x3 taps
+    ga.Cg = ga.c_split = Co;
+    ga.s[0] = ga.s[1] = mk_src(hw + 4, Co, h16, false);
+    ga.s[0].oy = ga.s[0].ox = ga.s[1].oy = ga.s[1].ox = 2;
+    gb.Cg = Ci;
+    gb.c_split = kind == 1 ? Ci / 2 : Ci;
+    gb.taps_h = gb.taps_w = 3;
+    const int cs = kind == 1 ? Ci / 2 : Ci;
+    gb.s[0] = mk_src(hw + 2, cs, h16, tf);
+    gb.s[1] = kind == 1 ? mk_src(hw + 2, cs, h16, false) : gb.s[0];
+    a.Mo = Co;
+    a.No = 9 * Ci;
+  } else {  // ga: the convT input X (Mo = its channels), gb: dY on the 2x grid, 2x2 stride 2
+    ga.Cg = ga.c_split = Co;
+    ga.s[0] = ga.s[1] = mk_src(hw, Co, h16, tf);
+    gb.Cg = gb.c_split = Ci;
+    gb.taps_h = gb.taps_w = 2;
+    gb.stride = 2;
+    gb.s[0] = gb.s[1] = mk_src(2 * hw, Ci, h16, false);
+    a.Mo = Co;
+    a.No = 4 * Ci;
+  }
+  a.P = nimg * hw * hw;
+  a.pix_per_split = 0;
+  a.out = g_dummy;
+  a.bf16 = prec != 0;
+  a.split = prec == 2;
+  if (slab) {
+    a.slab = g_dummy;
+    a.slab_bytes = (size_t)256 << 20;
+  }
+  a.accumulate = accumulate;
+  a.batch = batch;
+  if (batch > 1) {
+    a.batch_a = (long long)a.P * Co;
+    a.batch_b = (long long)a.P * Ci;
+    a.batch_out = (long long)a.Mo * a.No;
+  }
+  if (prec == 0) {
+    a.wino_ws = g_dummy;
+    a.wino_ws_bytes = (size_t)1 << 31;
+  }
+  return a;
+}
+
+static std::string selection_dump() {
+  using namespace unet;
+  std::string o;
+  const int chans[] = {64, 128, 256, 512, 1024}, grids[] = {4, 10, 30, 104};
+  const size_t slab_bytes = (size_t)256 << 20;
+  int idx = 0;
+  for (int kind = 0; kind < 4; ++kind)
+    for (int Cg : chans)
+      for (int N : chans)
+        for (int prec = 0; prec < 3; ++prec, ++idx) {
+          // the remaining options cycle so that every value meets every kind and precision
+          const int hw = grids[idx % 4], nimg = (idx / 4) % 2 ? 8 : 1, h16 = prec == 1 ? (idx / 8) % 4 != 0 : 0;
+          const bool tf = (idx / 3) % 2 != 0;
+          const int fwd = (idx / 5) % 2;
+          const IgemmArgs a = mk_igemm(kind, Cg, N, hw, nimg, h16, tf, fwd, prec);
+          appendf(o, "%s | kind %d h16 %d tf %d fwd %d n %d | heur %d |", igemm_key(a).c_str(), kind, h16, (int)tf, fwd,
+                  nimg, igemm_heuristic_tile(a));
+          for (const IgemmTile& t : igemm_tiles())
+            if (igemm_tile_fits(a, t.id))
+              appendf(o, " %d:%lld/%d", t.id, igemm_tile_count(a, t.id), igemm_tile_slots(t.id));
+          o += " | cand";
+          for (const GemmChoice& c : igemm_candidates(a, slab_bytes)) appendf(o, " %d:%d", c.tile, c.split);
+          // forced igemm_variant: the tile the heuristic launch runs and its flops, where they differ
+          const double base = igemm_exec_flops(a, GemmChoice{});
+          o += " | forced";
+          for (const IgemmTile& t : igemm_tiles()) {
+            g_tune_igemm = t.id;
+            const int h = igemm_heuristic_tile(a);
+            const double f = igemm_exec_flops(a, GemmChoice{});
+            if (h == t.id) appendf(o, f != base ? " %d:%.6g" : " %d", t.id, f);
+          }
+          g_tune_igemm = -1;
+          o += " | flops";
+          for (int t : {4, 21, 70, 71, 72, 73, 74, 75, 76, 77}) appendf(o, " %.6g", igemm_exec_flops(a, GemmChoice{t, 1}));
+          o += "\n";
+        }
+  const int knobs[] = {-1,  1,   2,   8,   10,  11,  12,  13,  14,  20,  21,  22,  23,  24,  25,  26,  27,  28,
+                       29,  30,  31,  32,  33,  40,  41,  42,  43,  44,  71,  74,  100, 101, 102, 103, 104, 110,
+                       111, 112, 113, 114, 126, 127, 128, 129, 130, 131, 132, 133, 140, 141, 142, 143, 144, 1071, 1074};
+  idx = 0;
+  for (int kind = 0; kind < 3; ++kind)
+    for (int Co : chans)
+      for (int Ci : chans)
+        for (int prec = 0; prec < 3; ++prec, ++idx) {
+          const int hw = grids[idx % 4], nimg = (idx / 4) % 2 ? 8 : 1, h16 = prec == 1 ? (idx / 8) % 4 != 0 : 0;
+          const bool tf = (idx / 3) % 2 != 0, slab = (idx / 2) % 3 != 0;
+          const int accumulate = (idx / 7) % 4 == 0, batch = (idx / 11) % 5 == 0 ? 16 : 1;
+          const WgradArgs a = mk_wgrad(kind, Co, Ci, hw, nimg, h16, tf, prec, slab, accumulate, batch);
+          for (int det = 0; det < 2; ++det) {
+            g_deterministic = det;
+            appendf(o, "%s | kind %d h16 %d tf %d slab %d acc %d batch %d n %d | fits", wgrad_key(a).c_str(), kind, h16,
+                    (int)tf, (int)slab, accumulate, batch, nimg);
+            for (const WgradTile& t : wgrad_tiles())
+              if (wgrad_tile_fits(a, t.id)) appendf(o, " %d", t.id);
+            o += " | cand";
+            for (const GemmChoice& c : wgrad_candidates(a))
+              appendf(o, " %d:%d%s", c.tile, c.split, wgrad_choice_deterministic(c) ? "d" : "");
+            if (det) {  // the knobs do not depend on the mode
+              o += "\n";
+              continue;
+            }
+            o += " | knob";  // wgrad_variant values that force something, and what
+            for (int k : knobs) {
+              g_tune_wgrad = k;
+              const GemmChoice r = resolve_forced_wgrad(a, k);
+              if (r.tile >= 0)
+                appendf(o, " %d:%d/%d,%d,%.6g", k, r.tile, r.split, wgrad_winograd_mt(a, GemmChoice{}),
+                        wgrad_exec_flops(a, GemmChoice{}));
+            }
+            g_tune_wgrad = -1;
+            appendf(o, " | mt %d %d flops %.6g %.6g", wgrad_winograd_mt(a, GemmChoice{71, 1}),
+                    wgrad_winograd_mt(a, GemmChoice{74, 1001}), wgrad_exec_flops(a, GemmChoice{71, 1}),
+                    wgrad_exec_flops(a, GemmChoice{0, 8}));
+            o += " || ";  // one record for both modes
+          }
+          g_deterministic = 0;
+        }
+  return o;
+}
+
+// argv[1]: the golden file; argv[2] == "--record": write it instead of comparing
+static void test_selection(const char* golden, bool record) {
+  const std::string full = selection_dump();
+  std::string got;  // per record: its key and the hash of all of it
+  for (size_t i = 0; i < full.size();) {
+    const size_t e = full.find('\n', i);
+    unsigned long long h = 1469598103934665603ull;
+    for (size_t k = i; k < e; ++k) h = (h ^ (unsigned char)full[k]) * 1099511628211ull;
+    got.append(full, i, full.find(" | ", i) - i);
+    appendf(got, " #%016llx\n", h);
+    i = e + 1;
+  }
+  if (record) {
+    FILE* f = std::fopen(golden, "w");
+    CHECK(f != nullptr);
+    if (f) {
+      std::fwrite(got.data(), 1, got.size(), f);
+      std::fclose(f);
+    }
+    return;
+  }
+  FILE* f = std::fopen(golden, "r");
+  CHECK(f != nullptr);
+  if (!f) return;
+  std::string want;
+  char buf[4096];
+  for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) want.append(buf, n);
+  std::fclose(f);
+  size_t i = 0, j = 0;
+  int line = 1, bad = 0;
+  while (i < got.size() || j < want.size()) {
+    const size_t ie = std::min(got.find('\n', i), got.size()), je = std::min(want.find('\n', j), want.size());
+    if (got.compare(i, ie - i, want, j, je - j) != 0 && ++bad <= 5) {
+      size_t f = 0;  // the full record of this line
+      for (int l = 1; l < line && f != std::string::npos; ++l) f = full.find('\n', f) + 1;
+      std::fprintf(stderr, "gemm selection line %d differs:\n  got  %s\n  want %s\n  record %s\n", line,
+                   got.substr(i, ie - i).c_str(), want.substr(j, je - j).c_str(),
+                   f < full.size() ? full.substr(f, full.find('\n', f) - f).c_str() : "");
+    }
+    i = std::min(ie + 1, got.size());
+    j = std::min(je + 1, want.size());
+    ++line;
+  }
+  CHECK(bad == 0);
+}
+
+int main(int argc, char** argv) {
   test_plans();
   test_lsap();
   test_tracker();
   test_misc();
+  if (argc > 1) test_selection(argv[1], argc > 2 && std::strcmp(argv[2], "--record") == 0);
+  else CHECK(!"usage: host_selftest tests/golden/gemm_selection.txt [--record]");
   if (fails) {
     std::fprintf(stderr, "%d check(s) failed\n", fails);
     return 1;

@@ -248,7 +248,7 @@ int c64_cus() {
 
 // 64 -> 64 channels, one bf16 source (no concat), packed bf16 B, whole K per
 // workgroup, 32-bit source offsets
-bool conv3_c64_fits(const IgemmArgs& a) {
+static bool conv3_c64_fits(const IgemmArgs& a) {
   const Gather& g = a.a;
   const Src& s = g.s[0];
   return a.bh != nullptr && a.bl == nullptr && a.N == 64 && g.Cg == 64 && g.c_split >= g.Cg && g.taps_h == 3 &&
@@ -256,12 +256,12 @@ bool conv3_c64_fits(const IgemmArgs& a) {
          a.ksplit <= 1 && (size_t)g.nimg * s.H * s.W * s.C * 2 < (1ull << 32) && c64_smem(a) <= 160 * 1024;
 }
 
-long long conv3_c64_tiles(const IgemmArgs& a) {
+static long long conv3_c64_tiles(const IgemmArgs& a) {
   const Gather& g = a.a;
   return (long long)g.nimg * ((g.Hg + kTH - 1) / kTH) * ((g.Wg + 31) / 32);
 }
 
-hipError_t go_conv3_c64(const IgemmArgs& a, hipStream_t s) {
+static hipError_t go_conv3_c64(const IgemmArgs& a, hipStream_t s) {
   if (!conv3_c64_fits(a)) return hipErrorInvalidValue;
   const bool xtf = a.a.s[0].scale != nullptr;
   static bool attr[2] = {false, false};
@@ -276,6 +276,15 @@ hipError_t go_conv3_c64(const IgemmArgs& a, hipStream_t s) {
   if (xtf) hipLaunchKernelGGL((k_conv3_c64<1>), dim3(grid), dim3(256), c64_smem(a), s, a);
   else hipLaunchKernelGGL((k_conv3_c64<0>), dim3(grid), dim3(256), c64_smem(a), s, a);
   return hipGetLastError();
+}
+
+// Forced only: measured slower than the ring tiles on the 64-channel layers it
+// targets.  Persistent, whole K per workgroup.
+IgemmTileRows conv3_c64_tile_rows() {
+  static const IgemmTile rows[] = {
+      {87, IgemmFamily::C64, kTH * 32, 64, 576, 1, 0, 0, 64, 0, true, false, false, false,
+       [](const IgemmArgs& a, const IgemmTile&) { return conv3_c64_fits(a); }, &go_conv3_c64, &conv3_c64_tiles, nullptr}};
+  return tile_rows(rows);
 }
 
 }  // namespace unet

@@ -324,30 +324,33 @@ static hipError_t go_conv3_dma(const IgemmArgs& a, hipStream_t s) {
   return tf ? go_conv3_dma_t<TH, BN, CH, WM, WN, MINW, 0>(a, s) : go_conv3_dma_t<TH, BN, CH, WM, WN, MINW, 1>(a, s);
 }
 
-// tile ids 63, 65-68 (igemm.hip tile_info): (TH, BN, CH, waves).  Measured and
+// bf16-stored A sources, no split operands
+static bool conv3_dma_fits(const IgemmArgs& a, const IgemmTile& t) {
+  const Gather& g = a.a;
+  const bool two = g.c_split < g.Cg;
+  return a.bh != nullptr && a.bl == nullptr && a.N % t.bn == 0 && g.taps_h == 3 && g.taps_w == 3 && g.stride == 1 &&
+         a.K == 9 * g.Cg && g.Cg % t.ch == 0 && g.c_split % t.ch == 0 && g.Cg <= 1024 && g.s[0].h16 &&
+         (!two || g.s[1].h16);
+}
+
+// Rows: TH x 32 pixels x BN columns, CH-channel chunks.  Measured and
 // dropped (profiles/r02_conv_dma_variants.txt): one-wave-per-SIMD shapes
 // (8x32/128 and 8x32/64 with 32-channel chunks at 4 waves) and 16x32/128 at 8
 // waves (spills in the register-staged form) ran 1.3-3x slower than k_conv3_bf.
-bool conv3_dma_tile_shape(int tile, int& th, int& bn, int& ch) {
-  switch (tile) {
-    case 63: th = 8; bn = 64; ch = 16; return true;
-    case 65: th = 16; bn = 64; ch = 16; return true;
-    case 66: th = 16; bn = 64; ch = 32; return true;
-    case 67: th = 8; bn = 64; ch = 16; return true;
-    case 68: th = 8; bn = 128; ch = 16; return true;
-    default: return false;
-  }
+template <int TH, int BN, int CH, int WM, int WN, int MINW>
+static constexpr IgemmTile conv3_dma_tile(int id, int slots) {
+  return conv3_tile(id, IgemmFamily::Conv3Dma, TH, 32, BN, CH, slots, true, false, true, conv3_dma_fits,
+                    &go_conv3_dma<TH, BN, CH, WM, WN, MINW>);
 }
-
-hipError_t go_conv3_dma_tile(const IgemmArgs& a, hipStream_t s, int tile) {
-  switch (tile) {
-    case 63: return go_conv3_dma<8, 64, 16, 4, 1, 2>(a, s);   // 4 waves, TM 2 x TN 2; 59 KB, 2 WG/CU
-    case 65: return go_conv3_dma<16, 64, 16, 4, 2, 2>(a, s);  // 8 waves, TM 4 x TN 1; 84 KB
-    case 66: return go_conv3_dma<16, 64, 32, 4, 2, 2>(a, s);  // 8 waves, TM 4 x TN 1; 160 KB
-    case 67: return go_conv3_dma<8, 64, 16, 8, 1, 4>(a, s);   // 8 waves, TM 1 x TN 2; 59 KB: 2 WG/CU, 4 waves/SIMD
-    case 68: return go_conv3_dma<8, 128, 16, 4, 2, 2>(a, s);  // 8 waves, TM 2 x TN 2 (64x64 per wave); 96 KB
-    default: return hipErrorInvalidValue;
-  }
+IgemmTileRows conv3_dma_tile_rows() {
+  static const IgemmTile rows[] = {
+      conv3_dma_tile<8, 64, 16, 4, 1, 2>(63, 2),   // 4 waves, TM 2 x TN 2; 59 KB, 2 WG/CU
+      conv3_dma_tile<16, 64, 16, 4, 2, 2>(65, 1),  // 8 waves, TM 4 x TN 1; 84 KB
+      conv3_dma_tile<16, 64, 32, 4, 2, 2>(66, 1),  // 8 waves, TM 4 x TN 1; 160 KB
+      conv3_dma_tile<8, 64, 16, 8, 1, 4>(67, 2),   // 8 waves, TM 1 x TN 2; 59 KB: 2 WG/CU, 4 waves/SIMD
+      conv3_dma_tile<8, 128, 16, 4, 2, 2>(68, 1),  // 8 waves, TM 2 x TN 2 (64x64 per wave); 96 KB
+  };
+  return tile_rows(rows);
 }
 
 }  // namespace unet

@@ -515,40 +515,42 @@ size_t conv3_flat_sk_slab_bytes(const IgemmArgs& a) {
   return ntb * (kSkSeg - 1) * ((size_t)kFlatTH * 32 * kFlatBN * 4 + 4);
 }
 
-bool conv3_flat_fits(const IgemmArgs& a, int tile) {
-  if (tile != 85 && tile != 86) return false;
+static bool conv3_flat_fits(const IgemmArgs& a, const IgemmTile&) {
   const Gather& g = a.a;
   const bool two = g.c_split < g.Cg, xtf = g.s[0].scale != nullptr;
   FlatMap fm;
   long long nt;
-  int grid;
   const bool base = a.bh != nullptr && a.bl == nullptr && a.N % kFlatBN == 0 && g.taps_h == 3 && g.taps_w == 3 &&
                     g.stride == 1 && a.K == 9 * g.Cg && g.Cg % kFlatCK == 0 && g.c_split % kFlatCK == 0 &&
                     g.s[0].h16 && (!two || (g.s[1].h16 && g.s[1].scale == nullptr)) &&
                     (!xtf || g.s[0].shift != nullptr) && flat_smem(a, xtf) <= 160 * 1024 &&
                     src_bytes(g.s[0], g.nimg) < (1ull << 32) && (!two || src_bytes(g.s[1], g.nimg) < (1ull << 32)) &&
                     (size_t)a.N * a.K * 2 < (1ull << 32) && flat_map(g, a.M, kFlatTH * 32, kFlatNPX, fm, nt);
-  if (!base) return false;
-  // stream-K: its partial slots live in the split-K slab (the plan checks the size)
-  return tile == 85 || (a.slab != nullptr && a.ksplit <= 1 && sk_deal(a, fm, grid));
+  return base;
+}
+// stream-K: its partial slots live in the split-K slab (the plan checks the
+// size: the row's slab_bytes)
+static bool conv3_flat_sk_fits(const IgemmArgs& a, const IgemmTile& t) {
+  FlatMap fm;
+  int grid;
+  return conv3_flat_fits(a, t) && a.slab != nullptr && a.ksplit <= 1 && sk_deal(a, fm, grid);
 }
 
-long long conv3_flat_tiles(const IgemmArgs& a, int tile) {
+template <bool SK>
+static long long conv3_flat_count(const IgemmArgs& a) {
   FlatMap fm;
   long long nt = 0;
   if (!flat_map(a.a, a.M, kFlatTH * 32, kFlatNPX, fm, nt)) return 0;
-  if (tile == 86) return flat_num_cus();
-  return nt * (a.N / kFlatBN);
+  return SK ? flat_num_cus() : nt * (a.N / kFlatBN);
 }
 
-hipError_t go_conv3_flat_tile(const IgemmArgs& a, hipStream_t s, int tile) {
-  if (!conv3_flat_fits(a, tile)) return hipErrorInvalidValue;
+template <bool sk>
+static hipError_t go_conv3_flat(const IgemmArgs& a, hipStream_t s) {
   constexpr int TH = kFlatTH, BN = kFlatBN, CK = kFlatCK, NPX = kFlatNPX, WM = 4, WN = 2, MINW = 2;
   const Gather& g = a.a;
   FlatMap fm;
   long long nt;
   flat_map(g, a.M, TH * 32, NPX, fm, nt);
-  const bool sk = tile == 86;
   int skg = 0;
   if (sk) {
     if (!sk_deal(a, fm, skg)) return hipErrorInvalidValue;
@@ -584,6 +586,19 @@ hipError_t go_conv3_flat_tile(const IgemmArgs& a, hipStream_t s, int tile) {
   }
 #undef FLAT_K
   return hipGetLastError();
+}
+
+// Flat tiles of kFlatTH x 32 consecutive pixels.  The stream-K form (one
+// workgroup per CU, equal runs of (tile, column block, chunk) units) is forced
+// only: measured slower on the shapes it targets.
+IgemmTileRows conv3_flat_tile_rows() {
+  static const IgemmTile rows[] = {
+      {85, IgemmFamily::Flat, kFlatTH * 32, kFlatBN, 9 * kFlatCK, 1, 0, 0, kFlatCK, 0, true, false, true, true,
+       conv3_flat_fits, &go_conv3_flat<false>, &conv3_flat_count<false>, nullptr},
+      {86, IgemmFamily::Flat, kFlatTH * 32, kFlatBN, 9 * kFlatCK, 1, 0, 0, kFlatCK, 0, true, false, false, false,
+       conv3_flat_sk_fits, &go_conv3_flat<true>, &conv3_flat_count<true>, &conv3_flat_sk_slab_bytes},
+  };
+  return tile_rows(rows);
 }
 
 }  // namespace unet

@@ -457,4 +457,17 @@ static hipError_t go_ring(const IgemmArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// A row of the igemm tile table: TH x 32 pixels x BN columns, CK-channel chunks.
+// Beyond conv3_ring_fits: the BN table must fit the LDS beside the ring, and
+// the persistent form takes the whole K per workgroup.
+template <int TH, int BN, int WM, int WN, int CK, int MINW, int PT>
+static constexpr IgemmTile ring_tile(int id, int slots) {
+  return conv3_tile(id, IgemmFamily::Ring, TH, 32, BN, CK, slots, true, false, PT == 0,
+                    [](const IgemmArgs& a, const IgemmTile& t) {
+                      return conv3_ring_fits(a, t) && !(PT && a.ksplit > 1) &&
+                             ring_smem<TH, BN, CK>(a, a.a.s[0].scale != nullptr) <= 160 * 1024;
+                    },
+                    &go_ring<TH, BN, WM, WN, CK, MINW, PT>);
+}
+
 }  // namespace unet

@@ -303,47 +303,26 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm_ring(const IgemmArgs a
 }
 
 // ---------------------------------------------------------------------------
-// tile ids (igemm.hip tile_info 91-99)
-//
-// The nine tiles' kernels compile in three translation units of three tiles
+// Tile rows.  The kernels compile in three translation units of three tiles
 // each: this file and gemm_ring_p1.hip / gemm_ring_p2.hip, which include it
 // with GEMM_RING_PART set (as one unit they took a third of a from-scratch
-// build's wall time).  Part 0 holds the shape tables and the dispatch.
+// build's wall time).  Part 0 holds the family's fits.
 // ---------------------------------------------------------------------------
 #ifndef GEMM_RING_PART
 #define GEMM_RING_PART 0
 #endif
-hipError_t go_gemm_ring_p1(const IgemmArgs& a, hipStream_t s, int tile);  // tiles 94-96
-hipError_t go_gemm_ring_p2(const IgemmArgs& a, hipStream_t s, int tile);  // tiles 97-99
 
 #if GEMM_RING_PART == 0
-bool gemm_ring_tile_shape(int tile, int& bm, int& bn) {
-  switch (tile) {
-    case 91: bm = 128; bn = 128; return true;  // 4 waves (2 x 2), BK 64, 4 stages: 128 KB
-    case 92: bm = 256; bn = 128; return true;  // 8 waves (4 x 2), BK 64, 3 stages: 144 KB
-    case 93: bm = 128; bn = 256; return true;  // 8 waves (2 x 4), BK 64, 3 stages: 144 KB
-    case 94: bm = 128; bn = 128; return true;  // 8 waves (2 x 4), BK 64, 4 stages: 128 KB
-    case 95: bm = 64; bn = 128; return true;   // 4 waves (1 x 4), BK 64, 4 stages: 96 KB
-    case 96: bm = 256; bn = 256; return true;  // 8 waves (2 x 4, 128 x 64 each), BK 32, 4 stages: 128 KB
-    case 97: bm = 256; bn = 128; return true;  // 8 waves (4 x 2), BK 32, 6 stages: 144 KB
-    case 98: bm = 128; bn = 256; return true;  // 8 waves (2 x 4), BK 32, 6 stages: 144 KB
-    case 99: bm = 128; bn = 128; return true;  // 4 waves (2 x 2), BK 32, 8 stages: 128 KB
-    default: return false;
-  }
-}
-
 // convT forward (1x1 gather, K = Cg) or convT input gradient (2x2 stride-2
 // gather, K = 4 Cg), bf16 sources and packed bf16 B, channel counts multiples
 // of 64, one source (no concat)
-bool gemm_ring_fits(const IgemmArgs& a, int tile) {
-  int bm, bn;
-  if (!gemm_ring_tile_shape(tile, bm, bn)) return false;
+bool gemm_ring_fits(const IgemmArgs& a, const IgemmTile& t) {
   const Gather& g = a.a;
   const bool t1 = g.taps_h == 1 && g.taps_w == 1 && g.stride == 1 && a.K == g.Cg;
   const bool t2 = g.taps_h == 2 && g.taps_w == 2 && g.stride == 2 && a.K == 4 * g.Cg && g.s[0].scale == nullptr;
   const double bytes = (double)g.nimg * g.s[0].H * g.s[0].W * g.s[0].C * 2;
   return (t1 || t2) && a.bh != nullptr && a.bl == nullptr && g.s[0].h16 && g.c_split >= g.Cg && g.Cg % 64 == 0 &&
-         g.Cg <= 2048 && a.N % bn == 0 && a.batch <= 1 && bytes < 4294967296.0 &&
+         g.Cg <= 2048 && a.N % t.bn == 0 && a.batch <= 1 && bytes < 4294967296.0 &&
          (double)a.N * a.K * 2 < 4294967296.0;
 }
 #endif  // GEMM_RING_PART == 0
@@ -374,32 +353,32 @@ static hipError_t go_gemm_ring(const IgemmArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// BM x BN per workgroup on WM x WN waves, BK-k stages, NSTG of them in the ring
+template <int BM, int BN, int WM, int WN, int BK, int NSTG>
+static constexpr IgemmTile gemm_ring_tile(int id) {
+  return {id, IgemmFamily::GemmRing, BM, BN, BK, 1, 0, 0, 0, 0, true, false, true, true, gemm_ring_fits,
+          &go_gemm_ring<BM, BN, WM, WN, BK, NSTG>, nullptr, nullptr};
+}
 #if GEMM_RING_PART == 0
-hipError_t go_gemm_ring_tile(const IgemmArgs& a, hipStream_t s, int tile) {
-  if (!gemm_ring_fits(a, tile)) return hipErrorInvalidValue;
-  switch (tile) {
-    case 91: return go_gemm_ring<128, 128, 2, 2, 64, 4>(a, s);
-    case 92: return go_gemm_ring<256, 128, 4, 2, 64, 3>(a, s);
-    case 93: return go_gemm_ring<128, 256, 2, 4, 64, 3>(a, s);
-    case 94: case 95: case 96: return go_gemm_ring_p1(a, s, tile);
-    default: return go_gemm_ring_p2(a, s, tile);
-  }
+IgemmTileRows gemm_ring_tile_rows() {
+  static const IgemmTile rows[] = {gemm_ring_tile<128, 128, 2, 2, 64, 4>(91),   // 128 KB
+                                   gemm_ring_tile<256, 128, 4, 2, 64, 3>(92),   // 144 KB
+                                   gemm_ring_tile<128, 256, 2, 4, 64, 3>(93)};  // 144 KB
+  return tile_rows(rows);
 }
 #elif GEMM_RING_PART == 1
-hipError_t go_gemm_ring_p1(const IgemmArgs& a, hipStream_t s, int tile) {
-  switch (tile) {
-    case 94: return go_gemm_ring<128, 128, 2, 4, 64, 4>(a, s);
-    case 95: return go_gemm_ring<64, 128, 1, 4, 64, 4>(a, s);
-    default: return go_gemm_ring<256, 256, 2, 4, 32, 4>(a, s);
-  }
+IgemmTileRows gemm_ring_p1_tile_rows() {
+  static const IgemmTile rows[] = {gemm_ring_tile<128, 128, 2, 4, 64, 4>(94),   // 128 KB
+                                   gemm_ring_tile<64, 128, 1, 4, 64, 4>(95),    // 96 KB
+                                   gemm_ring_tile<256, 256, 2, 4, 32, 4>(96)};  // 128 x 64 per wave; 128 KB
+  return tile_rows(rows);
 }
 #else
-hipError_t go_gemm_ring_p2(const IgemmArgs& a, hipStream_t s, int tile) {
-  switch (tile) {
-    case 97: return go_gemm_ring<256, 128, 4, 2, 32, 6>(a, s);
-    case 98: return go_gemm_ring<128, 256, 2, 4, 32, 6>(a, s);
-    default: return go_gemm_ring<128, 128, 2, 2, 32, 8>(a, s);
-  }
+IgemmTileRows gemm_ring_p2_tile_rows() {
+  static const IgemmTile rows[] = {gemm_ring_tile<256, 128, 4, 2, 32, 6>(97),   // 144 KB
+                                   gemm_ring_tile<128, 256, 2, 4, 32, 6>(98),   // 144 KB
+                                   gemm_ring_tile<128, 128, 2, 2, 32, 8>(99)};  // 128 KB
+  return tile_rows(rows);
 }
 #endif
 

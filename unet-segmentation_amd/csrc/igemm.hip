@@ -15,6 +15,7 @@
 // double buffered.  The next K-step's global loads are issued before the MFMA
 // block and consumed (transform + ds_write) after it, so each wave's HBM/L2
 // latency hides under its own 32 MFMAs (2048 cycles) plus its SIMD partners'.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 
@@ -22,19 +23,6 @@
 #include "ring_common.h"
 
 namespace unet {
-// convT weight gradient on an LDS-DMA ring of pixel stages (wgradT_ring.hip,
-// wgrad tiles 40-43)
-bool wgradT_ring_fits(const WgradArgs& a, int tile);
-hipError_t go_wgradT_ring(const WgradArgs& a, hipStream_t s, int tile, int per_cu);
-// conv3_flat.hip (tile 85: the ring on flat pixel tiles)
-bool conv3_flat_fits(const IgemmArgs& a, int tile);
-long long conv3_flat_tiles(const IgemmArgs& a, int tile);
-hipError_t go_conv3_flat_tile(const IgemmArgs& a, hipStream_t s, int tile);
-// conv3_c64.hip (tile 87: 64 -> 64 channels, resident weights, persistent)
-bool conv3_c64_fits(const IgemmArgs& a);
-long long conv3_c64_tiles(const IgemmArgs& a);
-hipError_t go_conv3_c64(const IgemmArgs& a, hipStream_t s);
-
 // Occupancy the register allocator must preserve: as many workgroups as the
 // LDS footprint admits per CU (without it hipcc moves the accumulators to
 // AGPRs and drops a wave per SIMD).
@@ -795,7 +783,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad3_f32(const WgradArgs args) {
   }
 }
 
-static bool wgrad3_f32_fits(const WgradArgs& a) {
+static bool wgrad3_f32_fits(const WgradArgs& a, const WgradTile&) {
   const Gather& g = a.gb;
   return !a.bf16 && g.taps_h == 3 && g.taps_w == 3 && g.stride == 1 && a.No == 9 * g.Cg && a.Mo % 64 == 0 &&
          g.Cg % 64 == 0 && (g.c_split % 64 == 0 || g.c_split >= g.Cg) && a.ga.Cg == a.Mo && a.ga.taps_h == 1 &&
@@ -1143,161 +1131,6 @@ int g_wino_wgrad_max = env_int("UNET_WINO_WGRAD_MAX", 6);
 int g_wino4_fwd_min_cg = env_int("UNET_WINO4_FWD_MIN_CG", 128);
 // ... and also up to this many ("wino4_fwd_small_cg" / UNET_WINO4_FWD_SMALL_CG)
 int g_wino4_fwd_small_cg = env_int("UNET_WINO4_FWD_SMALL_CG", 0);
-static int wino_tile_m(int tile) {
-  return tile == 70 || tile == 75 || tile == 77 ? 2 : tile == 71 || tile == 72 || tile == 73 || tile == 76 ? 4 : tile == 74 ? 6 : 0;
-}
-
-// igemm tile table: id -> (BM, BN, waves M x N, BK), resident workgroups per CU
-// (min of the LDS and VGPR limits of the built kernels).
-struct TileInfo {
-  int bm, bn, bk, slots;
-};
-static TileInfo tile_info(int id) {
-  switch (id) {
-    case 1: return {128, 128, 16, 3};
-    case 2: return {64, 128, 16, 4};
-    case 3: return {128, 128, 32, 2};
-    case 4: return {256, 128, 16, 2};
-    case 6: return {256, 64, 16, 2};
-    case 7: return {256, 64, 32, 1};
-    case 8: return {128, 64, 16, 4};
-    case 9: return {64, 128, 32, 2};
-    // LDS-DMA staged (k_igemm_g)
-    case 11: return {256, 128, 16, 2};
-    case 12: return {128, 128, 16, 3};
-    case 13: return {64, 128, 16, 4};
-    case 14: return {128, 64, 16, 4};
-    // bf16 operands, register staged (k_igemm_bf, igemm_bf16.hip)
-    case 21: return {256, 128, 32, 2};
-    case 22: return {128, 128, 32, 3};
-    case 23: return {128, 64, 32, 4};
-    case 24: return {64, 128, 32, 4};
-    case 25: return {256, 64, 32, 2};
-    case 26: return {128, 256, 32, 2};
-    // bf16 halo-tiled 3x3 (k_conv3_bf): bm = pixels per tile, bk = one
-    // 32-channel chunk x 9 taps (the split-K unit)
-    case 31: return {256, 64, 288, 2};
-    case 32: return {256, 64, 288, 2};
-    case 33: return {256, 64, 288, 2};
-    case 34: return {128, 128, 288, 1};
-    case 35: return {128, 64, 288, 2};
-    case 36: return {256, 128, 288, 1};
-    case 41: case 42: case 43: case 44: return {256, 64, 288, 1};  // persistent k_conv3p_bf
-    // bf16 halo-tiled 3x3 with LDS-DMA weights and a 2-stage ring (k_conv3_dma,
-    // conv3_dma.hip): bk = one channel chunk (16 or 32) x 9 taps
-    case 63: return {256, 64, 144, 2};
-    case 65: return {512, 64, 144, 1};
-    case 66: return {512, 64, 288, 1};
-    case 67: return {256, 64, 144, 2};
-    case 68: return {256, 128, 144, 1};
-    // bf16 3x3 with LDS-DMA halo and weight rings (k_conv3_ring, conv3_ring.hip):
-    // bk = one 64- or 32-channel chunk x 9 taps (the split-K unit)
-    case 81: return {256, 128, 576, 1};
-    case 82: return {256, 64, 288, 2};
-    case 83: return {128, 128, 288, 3};
-    case 84: return {256, 64, 576, 1};
-    // the ring on flat tiles of 256 consecutive pixels (k_conv3_flat, conv3_flat.hip)
-    case 85: return {256, 128, 576, 1};
-    // 85 stream-K: one workgroup per CU, equal runs of (tile, column block, chunk) units
-    case 86: return {256, 128, 576, 1};
-    // 64 -> 64 channels with the weights resident in LDS (k_conv3_c64, conv3_c64.hip): persistent
-    case 87: return {256, 64, 576, 1};
-    // 84 persistent (k_conv3_ring PT): whole K per workgroup
-    case 88: return {256, 64, 576, 1};
-    // bf16 convT forward / input gradient on LDS-DMA K rings (k_gemm_ring,
-    // gemm_ring.hip): 64-k stages
-    case 91: return {128, 128, 64, 1};
-    case 92: return {256, 128, 64, 1};
-    case 93: return {128, 256, 64, 1};
-    case 94: return {128, 128, 64, 1};
-    case 95: return {64, 128, 64, 1};
-    case 96: return {256, 256, 32, 1};
-    case 97: return {256, 128, 32, 1};
-    case 98: return {128, 256, 32, 1};
-    case 99: return {128, 128, 32, 1};
-    // Winograd F(2x2, 3x3) (winograd.hip): no K split
-    case 70: case 71: case 74: return {256, 64, 9, 2};
-    case 72: return {32, 32, 16, 1};
-    case 73: case 76: return {32, 64, 8, 1};
-    case 75: return {64, 64, 8, 1};
-    case 77: return {64, 32, 8, 2};
-    // fp32 halo-tiled 3x3 (k_conv3_f32): bk = one 16-channel chunk x 9 taps
-    case 51: return {256, 64, 144, 2};
-    case 52: return {256, 64, 144, 2};
-    case 53: return {256, 64, 144, 2};
-    case 54: return {128, 64, 144, 2};
-    default: return {0, 0, 0, 0};
-  }
-}
-
-static bool is_halo_tile(int tile) { return (tile >= 31 && tile <= 36) || (tile >= 41 && tile <= 44); }
-static bool is_dma_tile(int tile) { return tile == 63 || (tile >= 65 && tile <= 68); }
-static bool is_ring_tile(int tile) { return (tile >= 81 && tile <= 84) || tile == 88; }
-static bool is_gemm_ring_tile(int tile) { return tile >= 91 && tile <= 99; }
-static bool is_bf16_tile(int tile) {
-  return (tile >= 21 && tile <= 26) || is_halo_tile(tile) || is_dma_tile(tile) || is_ring_tile(tile) || tile == 85 || tile == 86 || tile == 87 ||
-         is_gemm_ring_tile(tile);
-}
-static bool is_halo32_tile(int tile) { return tile >= 51 && tile <= 54; }
-
-// A tile applies when the shape divides and the packed B operand is in the
-// tile's precision (fp32 `b` for tiles 1-14, bf16 `bh` for 21-26).
-bool igemm_tile_fits(const IgemmArgs& a, int tile) {
-  // every 3x3 forward conv feeds a BatchNorm (stats); the input gradients do
-  // not.  An eval forward is held to the forward caps too, so eval logits see
-  // the same arithmetic as the training forward's parity checks (ADVICE r03);
-  // run_forward marks every 3x3 forward conv explicitly (IgemmArgs::fwd,
-  // ADVICE r04) rather than the caps being inferred from the epilogue
-  const bool fwd = a.fwd != 0;
-  if (wino_tile_m(tile) > (fwd ? g_wino_max : g_wino_dgrad_max)) return false;
-  if (fwd && wino_tile_m(tile) >= 4 && a.a.Cg < g_wino4_fwd_min_cg && a.a.Cg > g_wino4_fwd_small_cg)
-    return false;
-  const TileInfo t = tile_info(tile);
-  const bool prec_ok = is_bf16_tile(tile) ? a.bh != nullptr && (a.bl == nullptr || bf16_tile_splits(tile))
-                                           : a.b != nullptr;
-  if (is_halo_tile(tile))  // 3x3 stride-1 gathers only (conv fwd / dgrad), K = 9 x Cg
-    return prec_ok && a.N % t.bn == 0 && a.a.taps_h == 3 && a.a.taps_w == 3 && a.a.stride == 1 &&
-           a.K == 9 * a.a.Cg && a.a.Cg % 32 == 0 && a.a.c_split % 32 == 0 && a.a.Cg <= 1024;
-  if (is_ring_tile(tile)) return conv3_ring_fits(a, tile);
-  if (tile == 85 || tile == 86) return conv3_flat_fits(a, tile);
-  if (tile == 87) return conv3_c64_fits(a);
-  if (is_gemm_ring_tile(tile)) return gemm_ring_fits(a, tile);
-  if (tile == 70 || tile == 71 || tile == 74) return wino_applies(a, tile == 70 ? 2 : tile == 71 ? 4 : 6);
-  if (tile == 72) return wino_fused_applies(a);
-  if (tile == 73) return wino_fused64_applies(a);
-  if (tile == 76) return wino_fused64p_applies(a);
-  if (tile == 75) return wino_fused2_applies(a, 64);
-  if (tile == 77) return wino_fused2_applies(a, 32);
-  if (is_dma_tile(tile)) {  // bf16-stored A sources, no split operands
-    const int ch = tile_info(tile).bk / 9;
-    const bool two = a.a.c_split < a.a.Cg;
-    return a.bh != nullptr && a.bl == nullptr && a.N % t.bn == 0 && a.a.taps_h == 3 && a.a.taps_w == 3 &&
-           a.a.stride == 1 && a.K == 9 * a.a.Cg && a.a.Cg % ch == 0 && a.a.c_split % ch == 0 && a.a.Cg <= 1024 &&
-           a.a.s[0].h16 && (!two || a.a.s[1].h16);
-  }
-  if (is_halo32_tile(tile))
-    return prec_ok && a.N % t.bn == 0 && a.a.taps_h == 3 && a.a.taps_w == 3 && a.a.stride == 1 &&
-           a.K == 9 * a.a.Cg && a.a.Cg % 16 == 0 && a.a.c_split % 16 == 0;
-  return t.bm > 0 && prec_ok && a.N % t.bn == 0 && a.K % t.bk == 0 && a.a.Cg % t.bk == 0 &&
-         a.a.c_split % t.bk == 0;
-}
-long long igemm_tile_count(const IgemmArgs& a, int tile) {
-  const TileInfo t = tile_info(tile);
-  if (t.bm == 0) return 0;
-  int th, tw, bn, ch;
-  if (tile == 85 || tile == 86) return conv3_flat_tiles(a, tile);
-  if (tile == 87) return conv3_c64_tiles(a);
-  if (halo_tile_shape(tile, th, tw, bn))
-    return (long long)a.a.nimg * ((a.a.Hg + th - 1) / th) * ((a.a.Wg + tw - 1) / tw) * (a.N / bn);
-  if (conv3_dma_tile_shape(tile, th, bn, ch) || conv3_ring_tile_shape(tile, th, bn, ch))
-    return (long long)a.a.nimg * ((a.a.Hg + th - 1) / th) * ((a.a.Wg + 31) / 32) * (a.N / bn);
-  return (long long)((a.M + t.bm - 1) / t.bm) * (a.N / t.bn);
-}
-int igemm_tile_slots(int tile) { return tile_info(tile).slots; }
-size_t igemm_slab_bytes(const IgemmArgs& a, int ksplit) {
-  return ksplit > 1 ? (size_t)ksplit * a.M * a.N * sizeof(float) : 0;
-}
-
 template <int BM, int BN, int WM, int WN, int BK>
 static hipError_t go_igemm(const IgemmArgs& a, hipStream_t s) {
   if (a.N % BN != 0 || a.K % BK != 0 || a.a.Cg % BK != 0 || a.a.c_split % BK != 0) return hipErrorInvalidValue;
@@ -1350,43 +1183,112 @@ static hipError_t go_halo32(const IgemmArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+
+// fp32 pixel-column weight gradient (k_wgrad) on launch_wgrad_v's grid
+template <int BM, int BN>
+static hipError_t go_wgrad_f32(const WgradArgs& a, hipStream_t s, dim3 grid) {
+  hipLaunchKernelGGL((k_wgrad<BM, BN, 2, 2>), grid, dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The igemm tile table (IgemmTile, unet_internal.h): this file's rows, then the
+// family files' rows in the order the autotuner tries them (it keeps the first
+// of equal times), forced-only rows last.  To add a tile: add its row beside
+// its kernel; nothing else lists tile ids.
+// ---------------------------------------------------------------------------
+// generic gathers: the shape divides and the packed B is in the tile's precision
+bool reg_tile_fits(const IgemmArgs& a, const IgemmTile& t) {
+  return igemm_prec_ok(a, t) && a.N % t.bn == 0 && a.K % t.bk == 0 && a.a.Cg % t.bk == 0 && a.a.c_split % t.bk == 0;
+}
+// 3x3 stride-1 gathers only (conv fwd / dgrad), K = 9 x Cg; the bf16 kernels'
+// BN table holds 1024 channels
+bool halo_tile_fits(const IgemmArgs& a, const IgemmTile& t) {
+  return igemm_prec_ok(a, t) && a.N % t.bn == 0 && a.a.taps_h == 3 && a.a.taps_w == 3 && a.a.stride == 1 &&
+         a.K == 9 * a.a.Cg && a.a.Cg % t.ch == 0 && a.a.c_split % t.ch == 0 && (!t.bf16 || a.a.Cg <= 1024);
+}
+template <int BM, int BN, int WM, int WN, int BK>
+static constexpr IgemmTile reg_tile(int id, int slots) {
+  return {id, IgemmFamily::Reg, BM, BN, BK, slots, 0, 0, 0, 0, false, false, true, true, reg_tile_fits,
+          &go_igemm<BM, BN, WM, WN, BK>, nullptr, nullptr};
+}
+template <int BM, int BN, int WM, int WN>  // LDS-DMA staged (k_igemm_g)
+static constexpr IgemmTile dma_tile(int id, int slots) {
+  return {id, IgemmFamily::Reg, BM, BN, 16, slots, 0, 0, 0, 0, false, false, true, true, reg_tile_fits,
+          &go_igemm_g<BM, BN, WM, WN>, nullptr, nullptr};
+}
+template <int TH, int TW, int BN, int WM, int WN, int MINW>  // fp32 halo-tiled 3x3 (k_conv3_f32), 16-channel chunks
+static constexpr IgemmTile halo32_tile(int id, int slots) {
+  return conv3_tile(id, IgemmFamily::Halo, TH, TW, BN, 16, slots, false, false, true, halo_tile_fits,
+                    &go_halo32<TH, TW, BN, WM, WN, MINW>);
+}
+static const IgemmTile kF32Tiles[] = {
+    reg_tile<256, 128, 4, 2, 16>(4, 2),    reg_tile<128, 128, 2, 2, 16>(1, 3),   reg_tile<64, 128, 2, 2, 16>(2, 4),
+    reg_tile<128, 64, 2, 2, 16>(8, 4),     reg_tile<256, 64, 4, 1, 16>(6, 2),    reg_tile<128, 128, 2, 2, 32>(3, 2),
+    reg_tile<64, 128, 2, 2, 32>(9, 2),     reg_tile<256, 64, 4, 1, 32>(7, 1),    dma_tile<256, 128, 4, 2>(11, 2),
+    dma_tile<128, 128, 2, 2>(12, 3),       dma_tile<64, 128, 2, 2>(13, 4),       dma_tile<128, 64, 2, 2>(14, 4),
+    halo32_tile<8, 32, 64, 8, 1, 4>(51, 2), halo32_tile<16, 16, 64, 8, 1, 4>(52, 2), halo32_tile<8, 32, 64, 4, 1, 2>(53, 2),
+    halo32_tile<8, 16, 64, 4, 1, 2>(54, 2),
+};
+
+const std::vector<IgemmTile>& igemm_tiles() {
+  static const std::vector<IgemmTile> table = [] {
+    std::vector<IgemmTile> v;
+    // (the persistent ring row after the Winograd rows: the order the tuner has always tried them in)
+    for (IgemmTileRows r : {tile_rows(kF32Tiles), igemm_bf16_tile_rows(), conv3_dma_tile_rows(), conv3_ring_tile_rows(),
+                            conv3_ring_pt_tile_rows(), conv3_flat_tile_rows(), wino_tile_rows(),
+                            conv3_ring_persistent_tile_rows(), gemm_ring_tile_rows(), gemm_ring_p1_tile_rows(),
+                            gemm_ring_p2_tile_rows(), conv3_c64_tile_rows()})
+      v.insert(v.end(), r.p, r.p + r.n);
+    std::stable_partition(v.begin(), v.end(), [](const IgemmTile& t) { return t.tuned; });
+    return v;
+  }();
+  return table;
+}
+
+const IgemmTile* igemm_tile(int id) {
+  static const std::vector<const IgemmTile*> by_id = [] {
+    std::vector<const IgemmTile*> v;
+    for (const IgemmTile& t : igemm_tiles()) {
+      if ((size_t)t.id >= v.size()) v.resize(t.id + 1, nullptr);
+      v[t.id] = &t;
+    }
+    return v;
+  }();
+  return id >= 0 && (size_t)id < by_id.size() ? by_id[id] : nullptr;
+}
+
+bool igemm_tile_fits(const IgemmArgs& a, int tile) {
+  const IgemmTile* t = igemm_tile(tile);
+  if (!t) return false;
+  // every 3x3 forward conv feeds a BatchNorm (stats); the input gradients do
+  // not.  An eval forward is held to the forward caps too, so eval logits see
+  // the same arithmetic as the training forward's parity checks (ADVICE r03);
+  // run_forward marks every 3x3 forward conv explicitly (IgemmArgs::fwd,
+  // ADVICE r04) rather than the caps being inferred from the epilogue
+  const bool fwd = a.fwd != 0;
+  if (t->wino_m > (fwd ? g_wino_max : g_wino_dgrad_max)) return false;
+  if (fwd && t->wino_m >= 4 && a.a.Cg < g_wino4_fwd_min_cg && a.a.Cg > g_wino4_fwd_small_cg) return false;
+  return t->fits(a, *t);
+}
+long long igemm_tile_count(const IgemmArgs& a, int tile) {
+  const IgemmTile* t = igemm_tile(tile);
+  if (!t) return 0;
+  if (t->count) return t->count(a);
+  if (t->th) return (long long)a.a.nimg * ((a.a.Hg + t->th - 1) / t->th) * ((a.a.Wg + t->tw - 1) / t->tw) * (a.N / t->bn);
+  return (long long)((a.M + t->bm - 1) / t->bm) * (a.N / t->bn);
+}
+int igemm_tile_slots(int tile) {
+  const IgemmTile* t = igemm_tile(tile);
+  return t ? t->slots : 0;
+}
+size_t igemm_slab_bytes(const IgemmArgs& a, int ksplit) {
+  return ksplit > 1 ? (size_t)ksplit * a.M * a.N * sizeof(float) : 0;
+}
+
 static hipError_t go_tile(const IgemmArgs& a, hipStream_t s, int tile) {
-  switch (tile) {
-    case 1: return go_igemm<128, 128, 2, 2, 16>(a, s);
-    case 2: return go_igemm<64, 128, 2, 2, 16>(a, s);
-    case 3: return go_igemm<128, 128, 2, 2, 32>(a, s);
-    case 4: return go_igemm<256, 128, 4, 2, 16>(a, s);
-    case 6: return go_igemm<256, 64, 4, 1, 16>(a, s);
-    case 7: return go_igemm<256, 64, 4, 1, 32>(a, s);
-    case 8: return go_igemm<128, 64, 2, 2, 16>(a, s);
-    case 9: return go_igemm<64, 128, 2, 2, 32>(a, s);
-    case 11: return go_igemm_g<256, 128, 4, 2>(a, s);
-    case 12: return go_igemm_g<128, 128, 2, 2>(a, s);
-    case 13: return go_igemm_g<64, 128, 2, 2>(a, s);
-    case 14: return go_igemm_g<128, 64, 2, 2>(a, s);
-    case 21: case 22: case 23: case 24: case 25: case 26:
-    case 31: case 32: case 33: case 34: case 35: case 36:
-    case 41: case 42: case 43: case 44: return go_igemm_bf16(a, s, tile);
-    case 63: case 65: case 66: case 67: case 68: return go_conv3_dma_tile(a, s, tile);
-    case 81: case 82: case 83: case 84: case 88: return go_conv3_ring_tile(a, s, tile);
-    case 85: case 86: return go_conv3_flat_tile(a, s, tile);
-    case 87: return go_conv3_c64(a, s);
-    case 91: case 92: case 93: case 94: case 95: case 96: case 97: case 98: case 99:
-      return go_gemm_ring_tile(a, s, tile);
-    case 70: return launch_wino(a, s, 2);
-    case 71: return launch_wino(a, s, 4);
-    case 74: return launch_wino(a, s, 6);
-    case 72: return launch_wino_fused(a, s);
-    case 73: return launch_wino_fused64(a, s);
-    case 76: return launch_wino_fused64p(a, s);
-    case 75: return launch_wino_fused2(a, s, 64);
-    case 77: return launch_wino_fused2(a, s, 32);
-    case 51: return go_halo32<8, 32, 64, 8, 1, 4>(a, s);
-    case 52: return go_halo32<16, 16, 64, 8, 1, 4>(a, s);
-    case 53: return go_halo32<8, 32, 64, 4, 1, 2>(a, s);
-    case 54: return go_halo32<8, 16, 64, 4, 1, 2>(a, s);
-    default: return hipErrorInvalidValue;
-  }
+  const IgemmTile* t = igemm_tile(tile);
+  return t ? t->go(a, s) : hipErrorInvalidValue;
 }
 
 static bool igemm_args_ok(const IgemmArgs& a) {
@@ -1399,8 +1301,13 @@ static bool igemm_args_ok(const IgemmArgs& a) {
 //  N >= 256, >= 1.5 x CUs 256x128 tiles: 8-wave 256x128    (+5..10 % on down1-3, up2)
 //  N = 128 with large M: 128x128
 //  otherwise (bottleneck, M <= ~20k pixels): 64x128 to fill the CUs
-static int heuristic_tile(const IgemmArgs& a) {
-  if (g_tune_igemm > 0 && igemm_tile_fits(a, g_tune_igemm)) return g_tune_igemm;
+GemmChoice resolve_forced_igemm(const IgemmArgs& a, int knob) {
+  return knob > 0 && igemm_tile_fits(a, knob) ? GemmChoice{knob, 1} : GemmChoice{};
+}
+
+int igemm_heuristic_tile(const IgemmArgs& a) {
+  const GemmChoice forced = resolve_forced_igemm(a, g_tune_igemm);
+  if (forced.tile >= 0) return forced.tile;
   const long long cus = num_cus();
   if (a.bh != nullptr) {  // bf16 operands: same shape rules over the bf16 tiles
     if (a.K % 32 || a.a.Cg % 32 || a.a.c_split % 32) return -1;
@@ -1428,150 +1335,193 @@ hipError_t launch_igemm(const IgemmArgs& a0, hipStream_t s) {
   if (!igemm_args_ok(a0)) return hipErrorInvalidValue;
   IgemmArgs a = a0;
   a.ksplit = 1;
-  return go_tile(a, s, heuristic_tile(a));
+  return go_tile(a, s, igemm_heuristic_tile(a));
 }
 
 hipError_t launch_igemm_v(const IgemmArgs& a0, hipStream_t s, GemmChoice c) {
   if (c.tile < 0) return launch_igemm(a0, s);
   if (!igemm_args_ok(a0) || !igemm_tile_fits(a0, c.tile)) return hipErrorInvalidValue;
+  const IgemmTile& t = *igemm_tile(c.tile);
   IgemmArgs a = a0;
-  const int nk = a.K / tile_info(c.tile).bk;
-  const bool wino = c.tile >= 70 && c.tile <= 77;
-  if ((c.tile == 70 || c.tile == 71 || c.tile == 74) && c.split >= 100) a.wino_choice.tile = c.split - 100;  // point GEMMs
-  int ks = c.split < 1 || wino ? 1 : (c.split > nk ? nk : c.split);
+  const int nk = a.K / t.bk;
+  // Winograd takes no K split: the unfused tiles' split code is 100 + the tile of their point GEMMs
+  if (t.family == IgemmFamily::Wino && c.split >= 100) a.wino_choice.tile = c.split - 100;
+  int ks = c.split < 1 || t.wino_m ? 1 : (c.split > nk ? nk : c.split);
   if (ks > 1) {  // no empty slice: ks = ceil(nk / ceil(nk / ks))
     const int per = (nk + ks - 1) / ks;
     ks = (nk + per - 1) / per;
   }
   a.ksplit = ks;
-  if (ks > 1 && (a.slab == nullptr || a.N % 64 != 0)) return hipErrorInvalidValue;
-  hipError_t e = go_tile(a, s, c.tile);
+  if (ks > 1 && (!t.ksplit || a.slab == nullptr || a.N % 64 != 0)) return hipErrorInvalidValue;
+  hipError_t e = t.go(a, s);
   if (e != hipSuccess || ks == 1) return e;
   dim3 grid((a.M + 127) / 128, a.N / 64);
   hipLaunchKernelGGL(k_splitk_epi, grid, dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
-// wgrad tile table: id -> (BM, BN); 0-4 fp32 (k_wgrad), 10-14 bf16 (k_wgrad_bf)
-static void wgrad_tile(int id, int& bm, int& bn) {
-  static const int t[5][2] = {{128, 128}, {128, 192}, {64, 192}, {64, 128}, {64, 64}};
-  static const int tb[5][2] = {{128, 128}, {128, 192}, {64, 128}, {64, 64}, {256, 128}};
-  bm = bn = 0;
-  if (id >= 0 && id < 5) { bm = t[id][0]; bn = t[id][1]; }
-  if (id >= 10 && id < 15) { bm = tb[id - 10][0]; bn = tb[id - 10][1]; }
+// ---------------------------------------------------------------------------
+// The wgrad tile table (WgradTile, unet_internal.h), assembled like the igemm one
+// ---------------------------------------------------------------------------
+static bool wgrad_column_fits(const WgradArgs& a, const WgradTile& t) {
+  return t.bf16 == (a.bf16 != 0) && a.Mo % t.bm == 0 && a.No % t.bn == 0;
 }
+template <int BM, int BN>
+static constexpr WgradTile wgrad_f32_tile(int id) {
+  return {id, WgradFamily::Column, BM, BN, 0, 0, 0, false, 8, wgrad_column_fits, nullptr, &go_wgrad_f32<BM, BN>};
+}
+template <int TH, int TW>  // fp32 halo-tiled 3x3 (k_wgrad3_f32): 64 co x 64 ci, all 9 taps
+static constexpr WgradTile wgrad3_f32_tile(int id) {
+  return {id, WgradFamily::Halo, 64, 64, TH, TW, 0, false, 4, wgrad3_f32_fits,
+          [](const WgradArgs& a, hipStream_t s, WgradMode m) { return go_wgrad3_f32<TH, TW>(a, s, m.per_cu); }, nullptr};
+}
+static const WgradTile kWgradF32Tiles[] = {wgrad_f32_tile<128, 128>(0), wgrad_f32_tile<128, 192>(1),
+                                           wgrad_f32_tile<64, 192>(2), wgrad_f32_tile<64, 128>(3),
+                                           wgrad_f32_tile<64, 64>(4)};
+static const WgradTile kWgrad3F32Tiles[] = {wgrad3_f32_tile<8, 16>(22), wgrad3_f32_tile<4, 32>(23)};
+
+const std::vector<WgradTile>& wgrad_tiles() {
+  static const std::vector<WgradTile> table = [] {
+    std::vector<WgradTile> v;
+    for (WgradTileRows r : {tile_rows(kWgradF32Tiles), wgrad_bf16_tile_rows(), wgrad3_bf16_tile_rows(),
+                            tile_rows(kWgrad3F32Tiles), wgrad3w_tile_rows(), wgrad3_ring_tile_rows(),
+                            wgradT_ring_tile_rows(), wino_wgrad_tile_rows()})
+      v.insert(v.end(), r.p, r.p + r.n);
+    return v;
+  }();
+  return table;
+}
+
+const WgradTile* wgrad_tile(int id) {
+  for (const WgradTile& t : wgrad_tiles())
+    if (t.id == id) return &t;
+  return nullptr;
+}
+
+// The one reading of a weight-gradient split code (the family's layout:
+// WgradFamily, unet_internal.h); codes <= 0 take the family's defaults
+WgradMode decode(const WgradTile& t, int code) {
+  WgradMode m{t.default_per_cu, -1, false};
+  switch (t.family) {
+    case WgradFamily::Column:
+      m.slab = code >= 100;
+      if (m.slab) code -= 100;
+      if (code > 0) m.per_cu = code;
+      break;
+    case WgradFamily::Halo:
+      if (code > 0) m.per_cu = code;
+      break;
+    case WgradFamily::Ring:
+    case WgradFamily::RingT:
+      if (code <= 0) code = t.default_per_cu;
+      m.slab = code >= 10;
+      m.per_cu = m.slab ? code - 10 : code;
+      break;
+    case WgradFamily::Wino:
+      m.slab = code >= 1000;
+      code %= 1000;
+      if (code >= 100) m.inner = code / 100 - 1;
+      if (code % 100 > 0) m.per_cu = code % 100;
+      break;
+  }
+  return m;
+}
+int encode(const WgradTile& t, WgradMode m) {
+  switch (t.family) {
+    case WgradFamily::Column: return m.per_cu + (m.slab ? 100 : 0);
+    case WgradFamily::Halo: return m.per_cu;
+    case WgradFamily::Ring:
+    case WgradFamily::RingT: return m.per_cu + (m.slab ? 10 : 0);
+    default: return m.per_cu + 100 * (m.inner + 1) + (m.slab ? 1000 : 0);
+  }
+}
+
 bool wgrad_tile_fits(const WgradArgs& a, int tile) {
-  if (wino_tile_m(tile) > g_wino_wgrad_max) return false;
-  // the Winograd weight gradients assign G^T Mw G to out: no accumulation
-  if (tile == 71 || tile == 74) return !a.accumulate && wino_wgrad_applies(a, tile == 71 ? 4 : 6);
-  if (a.batch > 1 && (tile < 0 || tile > 4)) return false;  // batched: fp32 pixel-column tiles only
-  if (tile == 20 || tile == 21) return wgrad3_fits(a);  // halo-tiled 3x3, all taps
-  if (tile == 22 || tile == 23) return wgrad3_f32_fits(a);  // fp32 twin
-  if (tile == 24 || tile == 25) return wgrad3w_fits(a, tile);  // wide halo-tiled 3x3, two-stage ring
-  if (tile >= 26 && tile <= 33) return wgrad3_ring_fits(a, tile);  // LDS-DMA ring of pixel tiles
-  if (tile >= 40 && tile <= 44) return wgradT_ring_fits(a, tile);  // convT: LDS-DMA ring of pixel stages
-  int bm, bn;
-  wgrad_tile(tile, bm, bn);
-  return bm > 0 && (tile >= 10) == (a.bf16 != 0) && a.Mo % bm == 0 && a.No % bn == 0;
+  const WgradTile* t = wgrad_tile(tile);
+  if (!t || t->wino_m > g_wino_wgrad_max) return false;
+  // batched: fp32 pixel-column tiles only
+  if (a.batch > 1 && (t->family != WgradFamily::Column || t->bf16)) return false;
+  return t->fits(a, *t);
+}
+
+// wgrad_variant (tests): a tile id forces that tile (bf16 launches: any; fp32:
+// the halo and Winograd tiles; pixel-column tiles then split knob-per-CU, as
+// the heuristic does); 100 + id forces it in slab mode (pixel-column tiles 2
+// per CU, ring tiles 1), 1000 + a Winograd id likewise; 1 the smallest fp32 tile
+GemmChoice resolve_forced_wgrad(const WgradArgs& a, int knob) {
+  const bool bf16 = a.bf16 != 0;
+  const WgradTile* t = wgrad_tile(knob);
+  if (t && (bf16 ? knob >= 10 : t->family != WgradFamily::Column) && wgrad_tile_fits(a, knob))
+    return {knob, t->family == WgradFamily::Column ? knob : 1};
+  t = wgrad_tile(knob - 1000);
+  if (t && t->family == WgradFamily::Wino && !bf16 && wgrad_tile_fits(a, t->id)) return {t->id, encode(*t, {0, -1, true})};
+  t = wgrad_tile(knob - 100);
+  if (t && t->bf16 == bf16 && wgrad_tile_fits(a, t->id)) {
+    if (t->family == WgradFamily::Column) return {t->id, encode(*t, {2, -1, true})};
+    if (t->family == WgradFamily::Ring || t->family == WgradFamily::RingT) return {t->id, encode(*t, {1, -1, true})};
+  }
+  if (knob == 1 && !bf16) return {4, 8};  // force the small tile (A/B tests)
+  return {};
+}
+
+static int wgrad_heuristic_tile(const WgradArgs& a) {
+  if (a.bf16) {
+    if (wgrad3_fits(a)) return 20;
+    if (a.Mo % 128 == 0 && a.No % 128 == 0) return 10;
+    return a.No % 128 == 0 ? 12 : 13;
+  }
+  if (a.Mo % 128 == 0 && a.No % 128 == 0) return 0;
+  if (a.Mo % 128 == 0 && a.No % 192 == 0) return 1;
+  if (a.No % 192 == 0) return 2;
+  return a.No % 128 == 0 ? 3 : 4;
 }
 
 hipError_t launch_wgrad_v(const WgradArgs& a0, hipStream_t s, GemmChoice c) {
   WgradArgs a = a0;
   if (a.Mo % 64 != 0 || a.P <= 0 || a.gb.Cg % 4 != 0 || a.gb.c_split % 4 != 0 || a.ga.Cg % 4 != 0)
     return hipErrorInvalidValue;
-  int tile = c.tile;
-  if (tile < 0 && a.bf16) {
-    if (g_tune_wgrad >= 10 && wgrad_tile_fits(a, g_tune_wgrad)) tile = g_tune_wgrad;  // forced (tests)
-    else if (g_tune_wgrad >= 126 && g_tune_wgrad <= 133 && wgrad_tile_fits(a, g_tune_wgrad - 100)) {
-      tile = g_tune_wgrad - 100;  // forced ring tile in slab mode (tests)
-      c.split = 11;
-    } else if (g_tune_wgrad >= 110 && g_tune_wgrad <= 114 && wgrad_tile_fits(a, g_tune_wgrad - 100)) {
-      c.tile = tile = g_tune_wgrad - 100;  // forced pixel-column tile in slab mode, 2 per CU (tests)
-      c.split = 102;
-    } else if (g_tune_wgrad >= 140 && g_tune_wgrad <= 144 && wgrad_tile_fits(a, g_tune_wgrad - 100)) {
-      tile = g_tune_wgrad - 100;  // forced convT ring tile in slab mode, 1 per CU (tests)
-      c.split = 11;
-    }
-    else if (wgrad3_fits(a)) tile = 20;
-    else if (a.Mo % 128 == 0 && a.No % 128 == 0) tile = 10;
-    else if (a.No % 128 == 0) tile = 12;
-    else tile = 13;
-  } else if (tile < 0) {
-    if ((g_tune_wgrad == 22 || g_tune_wgrad == 23 || g_tune_wgrad == 71 || g_tune_wgrad == 74) &&
-        wgrad_tile_fits(a, g_tune_wgrad))
-      tile = g_tune_wgrad;  // forced fp32 halo tile (tests)
-    else if ((g_tune_wgrad == 1071 || g_tune_wgrad == 1074) && wgrad_tile_fits(a, g_tune_wgrad - 1000)) {
-      tile = g_tune_wgrad - 1000;  // forced Winograd weight gradient in slab mode (tests; no Mw memset)
-      c.split = 1000;
-    } else if (g_tune_wgrad >= 100 && g_tune_wgrad <= 104 && wgrad_tile_fits(a, g_tune_wgrad - 100)) {
-      c.tile = tile = g_tune_wgrad - 100;  // forced fp32 pixel-column tile in slab mode, 2 per CU (tests)
-      c.split = 102;
-    } else if (g_tune_wgrad == 1) tile = 4;  // force the small tile (A/B tests)
-    else if (a.Mo % 128 == 0 && a.No % 128 == 0) tile = 0;
-    else if (a.Mo % 128 == 0 && a.No % 192 == 0) tile = 1;
-    else if (a.No % 192 == 0) tile = 2;
-    else if (a.No % 128 == 0) tile = 3;
-    else tile = 4;
-  }
-  if (!wgrad_tile_fits(a, tile)) return hipErrorInvalidValue;
-  if (tile == 71 || tile == 74) return launch_wino_wgrad(a, s, c.split, tile == 71 ? 4 : 6);
-  if (tile == 20 || tile == 21) return go_wgrad3_bf16(a, s, tile, c.split > 0 ? c.split : 4);
-  if (tile == 22) return go_wgrad3_f32<8, 16>(a, s, c.split > 0 ? c.split : 4);
-  if (tile == 24 || tile == 25) return go_wgrad3w_bf16(a, s, tile, c.split > 0 ? c.split : 1);
-  if (tile >= 26 && tile <= 33) return go_wgrad3_ring(a, s, tile, c.split > 0 ? c.split : 1);
-  if (tile >= 40 && tile <= 44) return go_wgradT_ring(a, s, tile, c.split > 0 ? c.split : 1);
-  if (tile == 23) return go_wgrad3_f32<4, 32>(a, s, c.split > 0 ? c.split : 4);
-  int bm, bn;
-  wgrad_tile(tile, bm, bn);
-  // split the pixel reduction so that the grid has ~`per_cu` workgroups per CU;
-  // codes >= 100: slab mode (plain-store split partials + one reduction pass)
-  const bool slab_mode = c.tile >= 0 && c.split >= 100;
-  if (slab_mode) c.split -= 100;
-  const int per_cu = c.tile >= 0 ? (c.split > 0 ? c.split : 8) : (g_tune_wgrad >= 2 ? g_tune_wgrad : 8);
+  const bool heuristic = c.tile < 0 && resolve_forced_wgrad(a, g_tune_wgrad).tile < 0;
+  if (heuristic) c.tile = wgrad_heuristic_tile(a);
+  else if (c.tile < 0) c = resolve_forced_wgrad(a, g_tune_wgrad);
+  if (!wgrad_tile_fits(a, c.tile)) return hipErrorInvalidValue;
+  const WgradTile& t = *wgrad_tile(c.tile);
+  WgradMode m = decode(t, c.split);
+  // the heuristic's pixel-column tiles: 8 workgroups per CU (or wgrad_variant >= 2 of them), atomics
+  if (heuristic && t.family == WgradFamily::Column) m = {g_tune_wgrad >= 2 ? g_tune_wgrad : 8, -1, false};
+  if (t.go) return t.go(a, s, m);
+  // pixel-column tiles: split the pixel reduction so that the grid has
+  // ~per_cu workgroups per CU
   int pps = 0;
-  const int splits = wgrad_splits(a, tile, per_cu, pps);
+  const int splits = wgrad_splits(a, t, m.per_cu, pps);
   a.pix_per_split = pps;
   const size_t plane = (size_t)a.Mo * a.No;
   // slab mode: one split writes its planes straight into out (plain stores),
   // more go through the slab and an assigning reduction; either way every
   // output element is written, so out needs no zeroing
-  if (!(slab_mode && wgrad_slab_fits(a, splits))) {
-    if (slab_mode) ++g_slab_fallbacks;  // split partials exceed the plan's wslab: atomics instead
+  if (!(m.slab && wgrad_slab_fits(a, splits))) {
+    if (m.slab) ++g_slab_fallbacks;  // split partials exceed the plan's wslab: atomics instead
     a.slab = nullptr;
   }
   else if (splits == 1) a.slab = a.out;
-  dim3 grid(a.Mo / bm, a.No / bn, splits * a.batch);
-  hipError_t e = hipSuccess;
-  if (tile >= 10) {
-    e = go_wgrad_bf16(a, s, tile, grid);
-  } else {
-    switch (tile) {
-      case 0: hipLaunchKernelGGL((k_wgrad<128, 128, 2, 2>), grid, dim3(256), 0, s, a); break;
-      case 1: hipLaunchKernelGGL((k_wgrad<128, 192, 2, 2>), grid, dim3(256), 0, s, a); break;
-      case 2: hipLaunchKernelGGL((k_wgrad<64, 192, 2, 2>), grid, dim3(256), 0, s, a); break;
-      case 3: hipLaunchKernelGGL((k_wgrad<64, 128, 2, 2>), grid, dim3(256), 0, s, a); break;
-      default: hipLaunchKernelGGL((k_wgrad<64, 64, 2, 2>), grid, dim3(256), 0, s, a); break;
-    }
-    e = hipGetLastError();
-  }
+  dim3 grid(a.Mo / t.bm, a.No / t.bn, splits * a.batch);
+  const hipError_t e = t.go_column(a, s, grid);
   if (e != hipSuccess || !a.slab || a.slab == a.out) return e;
   return launch_slab_reduce(a.slab, splits, a.batch, plane, a.batch_out, a.out, s);
 }
 
-int wgrad_splits(const WgradArgs& a, int tile, int per_cu, int& pps) {
-  int bm, bn;
-  wgrad_tile(tile, bm, bn);
-  const int tiles = (a.Mo / bm) * (a.No / bn) * a.batch;
+int wgrad_splits(const WgradArgs& a, const WgradTile& t, int per_cu, int& pps) {
+  const int tiles = (a.Mo / t.bm) * (a.No / t.bn) * a.batch;
   const int target = per_cu * num_cus();
   int splits = (target + tiles - 1) / tiles;
   const int max_splits = (a.P + 255) / 256;
   if (splits > max_splits) splits = max_splits;
   if (splits < 1) splits = 1;
   pps = (a.P + splits - 1) / splits;
-  const int kq = tile >= 10 ? 32 : 16;  // pixels per K-step
+  const int kq = t.bf16 ? 32 : 16;  // pixels per K-step
   pps = (pps + kq - 1) / kq * kq;
   return (a.P + pps - 1) / pps;
 }
+
 
 bool wgrad_slab_fits(const WgradArgs& a, int splits) {
   const size_t plane = (size_t)a.Mo * a.No;
@@ -1582,43 +1532,30 @@ bool wgrad_slab_fits(const WgradArgs& a, int splits) {
 hipError_t launch_wgrad(const WgradArgs& a, hipStream_t s) { return launch_wgrad_v(a, s, GemmChoice{}); }
 
 // The Winograd tile (mt = 4 / 6) launch_wgrad_v(a, s, c) runs for an fp32
-// launch, 0 if it runs another kernel (the same resolution of forced and
-// heuristic tiles as launch_wgrad_v)
+// launch, 0 if it runs another kernel
 int wgrad_winograd_mt(const WgradArgs& a, GemmChoice c) {
   if (a.bf16) return 0;
-  int tile = c.tile;
-  if (tile < 0) {
-    if ((g_tune_wgrad == 71 || g_tune_wgrad == 74) && wgrad_tile_fits(a, g_tune_wgrad)) tile = g_tune_wgrad;
-    else if ((g_tune_wgrad == 1071 || g_tune_wgrad == 1074) && wgrad_tile_fits(a, g_tune_wgrad - 1000))
-      tile = g_tune_wgrad - 1000;
-  }
-  if ((tile == 71 || tile == 74) && wgrad_tile_fits(a, tile)) return tile == 71 ? 4 : 6;
-  return 0;
+  if (c.tile < 0) c = resolve_forced_wgrad(a, g_tune_wgrad);
+  const WgradTile* t = wgrad_tile(c.tile);
+  return t && t->family == WgradFamily::Wino && wgrad_tile_fits(a, t->id) ? t->wino_m : 0;
+}
+
+static double wino_flops(int mt, const Gather& g, double rows, double cols) {
+  const double T = (double)g.nimg * ((g.Hg + mt - 1) / mt) * ((g.Wg + mt - 1) / mt);
+  return 2.0 * (mt + 2) * (mt + 2) * T * rows * cols;
 }
 
 double igemm_exec_flops(const IgemmArgs& a, GemmChoice c) {
-  int t = c.tile;
-  if (t < 0 && g_tune_igemm >= 70 && g_tune_igemm <= 77 && igemm_tile_fits(a, g_tune_igemm)) t = g_tune_igemm;
-  if (t >= 70 && t <= 77) {
-    const int mt = t == 70 || t == 75 || t == 77 ? 2 : t == 74 ? 6 : 4;
-    const Gather& g = a.a;
-    const double T = (double)g.nimg * ((g.Hg + mt - 1) / mt) * ((g.Wg + mt - 1) / mt);
-    return 2.0 * (mt + 2) * (mt + 2) * T * g.Cg * a.N;
-  }
+  if (c.tile < 0) c = resolve_forced_igemm(a, g_tune_igemm);
+  const IgemmTile* t = igemm_tile(c.tile);
+  if (t && t->wino_m) return wino_flops(t->wino_m, a.a, a.a.Cg, a.N);
   return 2.0 * a.M * (double)a.N * a.K;
 }
 
 double wgrad_exec_flops(const WgradArgs& a, GemmChoice c) {
-  int t = c.tile;
-  if (t < 0 && !a.bf16 && (g_tune_wgrad == 71 || g_tune_wgrad == 74) && wgrad_tile_fits(a, g_tune_wgrad))
-    t = g_tune_wgrad;
-  if (t < 0 && !a.bf16 && (g_tune_wgrad == 1071 || g_tune_wgrad == 1074) && wgrad_tile_fits(a, g_tune_wgrad - 1000))
-    t = g_tune_wgrad - 1000;
-  if (t == 71 || t == 74) {
-    const int mt = t == 71 ? 4 : 6;
-    const double T = (double)a.gb.nimg * ((a.gb.Hg + mt - 1) / mt) * ((a.gb.Wg + mt - 1) / mt);
-    return 2.0 * (mt + 2) * (mt + 2) * T * a.Mo * a.gb.Cg;
-  }
+  if (c.tile < 0) c = resolve_forced_wgrad(a, g_tune_wgrad);
+  const WgradTile* t = wgrad_tile(c.tile);
+  if (t && t->wino_m) return wino_flops(t->wino_m, a.gb, a.Mo, a.gb.Cg);
   return 2.0 * a.P * (double)a.Mo * a.No;
 }
 

@@ -1247,7 +1247,7 @@ static hipError_t go_wgrad3(const WgradArgs& a, hipStream_t s, int per_cu) {
   return hipGetLastError();
 }
 
-// halo-tiled 3x3 weight gradient (tiles 20: 8x16, 21: 4x32 output pixels per step)
+// halo-tiled 3x3 weight gradient
 bool wgrad3_fits(const WgradArgs& a) {
   const Gather& g = a.gb;
   return a.bf16 && g.taps_h == 3 && g.taps_w == 3 && g.stride == 1 && a.No == 9 * g.Cg && a.Mo % 64 == 0 &&
@@ -1256,28 +1256,26 @@ bool wgrad3_fits(const WgradArgs& a) {
          !(a.split && a.ga.s[0].h16);
 }
 
-hipError_t go_wgrad3_bf16(const WgradArgs& a, hipStream_t s, int tile, int per_cu) {
+// D16: dY stored bf16; split operands take fp32 dY only (wgrad3_fits)
+template <int TH, int TW>
+static hipError_t go_wgrad3_bf16(const WgradArgs& a, hipStream_t s, WgradMode m) {
   if (!wgrad3_fits(a)) return hipErrorInvalidValue;
-  const bool d16 = a.ga.s[0].h16 != 0;
-  if (a.split) {
-    switch (tile) {
-      case 20: return go_wgrad3<8, 16, 0, 1>(a, s, per_cu);
-      case 21: return go_wgrad3<4, 32, 0, 1>(a, s, per_cu);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  switch (tile * 2 + (d16 ? 1 : 0)) {
-    case 40: return go_wgrad3<8, 16, 0, 0>(a, s, per_cu);
-    case 41: return go_wgrad3<8, 16, 1, 0>(a, s, per_cu);
-    case 42: return go_wgrad3<4, 32, 0, 0>(a, s, per_cu);
-    case 43: return go_wgrad3<4, 32, 1, 0>(a, s, per_cu);
-    default: return hipErrorInvalidValue;
-  }
+  if (a.split) return go_wgrad3<TH, TW, 0, 1>(a, s, m.per_cu);
+  return a.ga.s[0].h16 ? go_wgrad3<TH, TW, 1, 0>(a, s, m.per_cu) : go_wgrad3<TH, TW, 0, 0>(a, s, m.per_cu);
+}
+template <int TH, int TW>  // 64 co x 64 ci per workgroup, TH x TW output pixels per step
+static constexpr WgradTile wgrad3_tile(int id) {
+  return {id, WgradFamily::Halo, 64, 64, TH, TW, 0, true, 4,
+          [](const WgradArgs& a, const WgradTile&) { return wgrad3_fits(a); }, &go_wgrad3_bf16<TH, TW>, nullptr};
+}
+WgradTileRows wgrad3_bf16_tile_rows() {
+  static const WgradTile rows[] = {wgrad3_tile<8, 16>(20), wgrad3_tile<4, 32>(21)};
+  return tile_rows(rows);
 }
 
 // ---------------------------------------------------------------------------
 // k_wgrad3w_bf: k_wgrad3_bf with a wider workgroup tile and a two-stage ring
-// (wgrad tiles 24: 128 co x 64 ci, 25: 64 co x 128 ci; bf16-stored dY and X).
+// (128 co x 64 ci or 64 co x 128 ci per workgroup; bf16-stored dY and X).
 // k_wgrad3_bf's waves hold 32 co x 32 ci x 5 taps: per 16-pixel k step 12
 // transposed LDS reads feed 5 MFMAs, which saturates the LDS (~150 B/clk per CU
 // at full MFMA rate against 128) -- and with one staging buffer the next
@@ -1471,12 +1469,12 @@ __global__ __launch_bounds__(512, 1) void k_wgrad3w_bf(const WgradArgs args, int
     }
 }
 
-bool wgrad3w_fits(const WgradArgs& a, int tile) {
-  const int bco = tile == 24 ? 128 : 64, bci = tile == 24 ? 64 : 128;
+static bool wgrad3w_fits(const WgradArgs& a, const WgradTile& t) {
+  const int bco = t.bm, bci = t.bn;
   const Gather& g = a.gb;
   const bool two = g.c_split < g.Cg;
-  return (tile == 24 || tile == 25) && wgrad3_fits(a) && !a.split && a.ga.s[0].h16 && g.s[0].h16 &&
-         (!two || g.s[1].h16) && a.Mo % bco == 0 && g.Cg % bci == 0 && (!two || g.c_split % bci == 0);
+  return wgrad3_fits(a) && !a.split && a.ga.s[0].h16 && g.s[0].h16 && (!two || g.s[1].h16) && a.Mo % bco == 0 &&
+         g.Cg % bci == 0 && (!two || g.c_split % bci == 0);
 }
 
 template <int BCO, int BCI>
@@ -1496,9 +1494,14 @@ static hipError_t go_wgrad3w(const WgradArgs& a, hipStream_t s, int per_cu) {
   return hipGetLastError();
 }
 
-hipError_t go_wgrad3w_bf16(const WgradArgs& a, hipStream_t s, int tile, int per_cu) {
-  if (!wgrad3w_fits(a, tile)) return hipErrorInvalidValue;
-  return tile == 24 ? go_wgrad3w<128, 64>(a, s, per_cu) : go_wgrad3w<64, 128>(a, s, per_cu);
+template <int BCO, int BCI>  // 8 x 16 output pixels per step; one resident workgroup per CU
+static constexpr WgradTile wgrad3w_tile(int id) {
+  return {id, WgradFamily::Halo, BCO, BCI, 8, 16, 0, true, 1, wgrad3w_fits,
+          [](const WgradArgs& a, hipStream_t s, WgradMode m) { return go_wgrad3w<BCO, BCI>(a, s, m.per_cu); }, nullptr};
+}
+WgradTileRows wgrad3w_tile_rows() {
+  static const WgradTile rows[] = {wgrad3w_tile<128, 64>(24), wgrad3w_tile<64, 128>(25)};
+  return tile_rows(rows);
 }
 
 // ---------------------------------------------------------------------------
@@ -1528,8 +1531,7 @@ hipError_t launch_f2bf(const float* in, uint16_t* out, size_t n, hipStream_t s, 
 }
 
 // ---------------------------------------------------------------------------
-// launchers (tile ids: igemm.hip tile_info 21-26, 31-36, 41-44; wgrad_tile
-// 10-14, 20-21).  Split operands (a.bl / a.split) select the SPLIT kernels.
+// launchers and tile rows.  Split operands (a.bl / a.split) select the SPLIT kernels.
 // ---------------------------------------------------------------------------
 template <int BM, int BN, int WM, int WN, int SPLIT>
 static hipError_t go_bf_t(const IgemmArgs& a, hipStream_t s) {
@@ -1599,52 +1601,37 @@ static hipError_t go_halo_p(const IgemmArgs& a, hipStream_t s, int waves_of_cus)
   return hipGetLastError();
 }
 
-// halo tile shapes: id -> (TH, TW, BN); see go_igemm_bf16
-bool halo_tile_shape(int tile, int& th, int& tw, int& bn) {
-  switch (tile) {
-    case 31: th = 8; tw = 32; bn = 64; return true;
-    case 32: th = 8; tw = 32; bn = 64; return true;
-    case 33: th = 16; tw = 16; bn = 64; return true;
-    case 34: th = 4; tw = 32; bn = 128; return true;
-    case 35: th = 8; tw = 16; bn = 64; return true;
-    case 36: th = 8; tw = 32; bn = 128; return true;
-    case 41: case 43: th = 8; tw = 32; bn = 64; return true;
-    case 42: case 44: th = 16; tw = 16; bn = 64; return true;
-    // fp32 k_conv3_f32 (igemm.hip)
-    case 51: case 53: th = 8; tw = 32; bn = 64; return true;
-    case 52: th = 16; tw = 16; bn = 64; return true;
-    case 54: th = 8; tw = 16; bn = 64; return true;
-    default: return false;
-  }
+// Rows of the igemm tile table.  Split-operand kernels exist for the register-
+// staged tiles and the halo tiles go_halo builds one for (the LDS of the 128-
+// column tiles does not hold the lo planes, 4 accumulator tiles per wave would
+// spill); the persistent kernel's double buffer has no room for them.
+template <int BM, int BN, int WM, int WN>
+static constexpr IgemmTile bf_tile(int id, int slots) {
+  return {id, IgemmFamily::Reg, BM, BN, kBfBK, slots, 0, 0, 0, 0, true, true, true, true,
+          reg_tile_fits, &go_bf<BM, BN, WM, WN>, nullptr, nullptr};
 }
-
-// tiles with a split-operand kernel (the LDS of 34/36 and the persistent
-// kernel's double buffer do not hold the lo planes; 32's 4 accumulator tiles
-// per wave would spill)
-bool bf16_tile_splits(int tile) { return (tile >= 21 && tile <= 26) || tile == 31 || tile == 33 || tile == 35; }
-
-hipError_t go_igemm_bf16(const IgemmArgs& a, hipStream_t s, int tile) {
-  if (a.bl && !bf16_tile_splits(tile)) return hipErrorInvalidValue;
-  switch (tile) {
-    case 31: return go_halo<8, 32, 64, 8, 1, 4>(a, s);
-    case 32: return go_halo<8, 32, 64, 4, 1, 2>(a, s);
-    case 33: return go_halo<16, 16, 64, 8, 1, 4>(a, s);
-    case 34: return go_halo<4, 32, 128, 4, 2, 2>(a, s);
-    case 35: return go_halo<8, 16, 64, 4, 1, 2>(a, s);
-    case 36: return go_halo<8, 32, 128, 4, 2, 2>(a, s);
-    // persistent pipelined (k_conv3p_bf): 1 or 2 rounds of workgroups per CU
-    case 41: return go_halo_p<8, 32>(a, s, 1);
-    case 42: return go_halo_p<16, 16>(a, s, 1);
-    case 43: return go_halo_p<8, 32>(a, s, 2);
-    case 44: return go_halo_p<16, 16>(a, s, 2);
-    case 21: return go_bf<256, 128, 4, 2>(a, s);
-    case 22: return go_bf<128, 128, 2, 2>(a, s);
-    case 23: return go_bf<128, 64, 2, 2>(a, s);
-    case 24: return go_bf<64, 128, 2, 2>(a, s);
-    case 25: return go_bf<256, 64, 4, 1>(a, s);
-    case 26: return go_bf<128, 256, 2, 4>(a, s);
-    default: return hipErrorInvalidValue;
-  }
+template <int TH, int TW, int BN, int WM, int WN, int MINW>
+static constexpr IgemmTile halo_tile(int id, int slots) {
+  constexpr bool x3 = conv3_bf_smem<TH, TW, BN, 1>(1024) <= kLdsBytes && (TH * TW / 32 / WM) * (BN / (WN * 32)) <= 2;
+  return conv3_tile(id, IgemmFamily::Halo, TH, TW, BN, 32, slots, true, x3, true, halo_tile_fits,
+                    &go_halo<TH, TW, BN, WM, WN, MINW>);
+}
+// persistent pipelined (k_conv3p_bf): ROUNDS rounds of workgroups per CU
+template <int TH, int TW, int ROUNDS>
+static constexpr IgemmTile halo_p_tile(int id) {
+  return conv3_tile(id, IgemmFamily::Halo, TH, TW, 64, 32, 1, true, false, true, halo_tile_fits,
+                    [](const IgemmArgs& a, hipStream_t s) { return go_halo_p<TH, TW>(a, s, ROUNDS); });
+}
+IgemmTileRows igemm_bf16_tile_rows() {
+  static const IgemmTile rows[] = {
+      bf_tile<256, 128, 4, 2>(21, 2),        bf_tile<128, 128, 2, 2>(22, 3),        bf_tile<128, 64, 2, 2>(23, 4),
+      bf_tile<64, 128, 2, 2>(24, 4),         bf_tile<256, 64, 4, 1>(25, 2),         bf_tile<128, 256, 2, 4>(26, 2),
+      halo_tile<8, 32, 64, 8, 1, 4>(31, 2),  halo_tile<8, 32, 64, 4, 1, 2>(32, 2),  halo_tile<16, 16, 64, 8, 1, 4>(33, 2),
+      halo_tile<4, 32, 128, 4, 2, 2>(34, 1), halo_tile<8, 16, 64, 4, 1, 2>(35, 2),  halo_tile<8, 32, 128, 4, 2, 2>(36, 1),
+      halo_p_tile<8, 32, 1>(41),             halo_p_tile<16, 16, 1>(42),            halo_p_tile<8, 32, 2>(43),
+      halo_p_tile<16, 16, 2>(44),
+  };
+  return tile_rows(rows);
 }
 
 template <int BM, int BN, int WM, int WN, int AH, int BH, int SPLIT>
@@ -1657,32 +1644,34 @@ static hipError_t go_wgrad_bf_t(const WgradArgs& a, hipStream_t s, dim3 grid) {
   return hipGetLastError();
 }
 
-template <int AH, int BH, int SPLIT>
-static hipError_t wgrad_bf_tile(const WgradArgs& a, hipStream_t s, int tile, dim3 grid) {
-  switch (tile) {
-    case 10: return go_wgrad_bf_t<128, 128, 2, 2, AH, BH, SPLIT>(a, s, grid);
-    case 11: return go_wgrad_bf_t<128, 192, 2, 2, AH, BH, SPLIT>(a, s, grid);
-    case 12: return go_wgrad_bf_t<64, 128, 2, 2, AH, BH, SPLIT>(a, s, grid);
-    case 13: return go_wgrad_bf_t<64, 64, 2, 2, AH, BH, SPLIT>(a, s, grid);
-    case 14: return go_wgrad_bf_t<256, 128, 4, 2, AH, BH, SPLIT>(a, s, grid);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-hipError_t go_wgrad_bf16(const WgradArgs& a, hipStream_t s, int tile, dim3 grid) {
+// AH / BH: dY / X stored bf16 (BH 2: the two concat sources differ)
+template <int BM, int BN, int WM, int WN>
+static hipError_t go_wgrad_bf(const WgradArgs& a, hipStream_t s, dim3 grid) {
   if (!a.bf16 || a.pix_per_split % kBfBK != 0) return hipErrorInvalidValue;
   const int ah = a.ga.s[0].h16;
   const bool two = a.gb.c_split < a.gb.Cg;
   const int bh = two && a.gb.s[0].h16 != a.gb.s[1].h16 ? 2 : a.gb.s[0].h16;
-  if (a.split) return ah == 0 && bh == 0 ? wgrad_bf_tile<0, 0, 1>(a, s, tile, grid) : hipErrorInvalidValue;
+  if (a.split) return ah == 0 && bh == 0 ? go_wgrad_bf_t<BM, BN, WM, WN, 0, 0, 1>(a, s, grid) : hipErrorInvalidValue;
   switch (ah * 3 + bh) {
-    case 0: return wgrad_bf_tile<0, 0, 0>(a, s, tile, grid);
-    case 1: return wgrad_bf_tile<0, 1, 0>(a, s, tile, grid);
-    case 2: return wgrad_bf_tile<0, 2, 0>(a, s, tile, grid);
-    case 3: return wgrad_bf_tile<1, 0, 0>(a, s, tile, grid);
-    case 4: return wgrad_bf_tile<1, 1, 0>(a, s, tile, grid);
-    default: return wgrad_bf_tile<1, 2, 0>(a, s, tile, grid);
+    case 0: return go_wgrad_bf_t<BM, BN, WM, WN, 0, 0, 0>(a, s, grid);
+    case 1: return go_wgrad_bf_t<BM, BN, WM, WN, 0, 1, 0>(a, s, grid);
+    case 2: return go_wgrad_bf_t<BM, BN, WM, WN, 0, 2, 0>(a, s, grid);
+    case 3: return go_wgrad_bf_t<BM, BN, WM, WN, 1, 0, 0>(a, s, grid);
+    case 4: return go_wgrad_bf_t<BM, BN, WM, WN, 1, 1, 0>(a, s, grid);
+    default: return go_wgrad_bf_t<BM, BN, WM, WN, 1, 2, 0>(a, s, grid);
   }
+}
+template <int BM, int BN, int WM, int WN>
+static constexpr WgradTile wgrad_bf_tile(int id) {
+  return {id, WgradFamily::Column, BM, BN, 0, 0, 0, true, 8,
+          [](const WgradArgs& a, const WgradTile& t) { return a.bf16 != 0 && a.Mo % t.bm == 0 && a.No % t.bn == 0; },
+          nullptr, &go_wgrad_bf<BM, BN, WM, WN>};
+}
+WgradTileRows wgrad_bf16_tile_rows() {
+  static const WgradTile rows[] = {wgrad_bf_tile<128, 128, 2, 2>(10), wgrad_bf_tile<128, 192, 2, 2>(11),
+                                   wgrad_bf_tile<64, 128, 2, 2>(12), wgrad_bf_tile<64, 64, 2, 2>(13),
+                                   wgrad_bf_tile<256, 128, 4, 2>(14)};
+  return tile_rows(rows);
 }
 
 }  // namespace unet

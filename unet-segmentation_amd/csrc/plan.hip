@@ -28,7 +28,6 @@ using namespace unet;
 
 namespace unet {
 extern int g_wino_max, g_wino_dgrad_max, g_wino_wgrad_max, g_wino4_fwd_min_cg, g_wino4_fwd_small_cg;  // igemm.hip (Winograd tile caps)
-size_t conv3_flat_sk_slab_bytes(const IgemmArgs& a);  // conv3_flat.hip (tile 86: stream-K partial slots)
 // unet_set_tuning("autotune", v) or UNET_AUTOTUNE (default on)
 int g_autotune = getenv("UNET_AUTOTUNE") ? atoi(getenv("UNET_AUTOTUNE")) : 1;
 // unet_set_tuning("concurrent", v) or UNET_CONCURRENT (default on): weight
@@ -327,6 +326,8 @@ int env_autotune() { return unet::g_autotune; }
 
 constexpr size_t kSlabBudget = 256ull << 20;  // split-K partials (fp32)
 
+}  // namespace
+namespace unet {  // declared in unet_internal.h (the host self test reads them)
 // Version of the GEMM variant tables (tile ids and their kernels): part of every
 // tuning key, so a database written by a build with another tile set is never
 // replayed (its lines simply miss).  Bump whenever a tile id changes meaning.
@@ -359,22 +360,18 @@ std::string wgrad_key(const WgradArgs& a) {
   return b;
 }
 
-// a weight-gradient variant that adds no fp32 atomics: slab modes (ring per_cu
-// codes 11 / 12, pixel-column codes 101-104, Winograd codes >= 1000: split
+// a weight-gradient variant that adds no fp32 atomics: slab modes (split
 // partials by plain stores, summed by k_wr_reduce in a fixed order; one split
 // stores straight into the gradient).  A slab launch whose partials exceed
 // the plan's slab falls back to atomics and counts in unet_slab_fallbacks().
 bool wgrad_choice_deterministic(const GemmChoice& g) {
-  if (g.tile == 71 || g.tile == 74) return g.split >= 1000;
-  if (g.tile >= 26 && g.tile <= 33) return g.split >= 10;
-  if (g.tile >= 40 && g.tile <= 44) return g.split >= 10;
-  if (g.tile >= 0 && g.tile <= 14) return g.split >= 100;
-  return false;
+  const WgradTile* t = wgrad_tile(g.tile);
+  return t && t->family != WgradFamily::Halo && decode(*t, g.split).slab;
 }
 
 // UNET_TUNE_SKIP="73,74": tile ids the autotuner never tries (A/B experiments
 // on accuracy or speed; igemm and wgrad ids alike)
-bool tune_skipped(int tile) {
+static bool tune_skipped(int tile) {
   static const std::vector<int> skip = [] {
     std::vector<int> v;
     if (const char* e = getenv("UNET_TUNE_SKIP"))
@@ -395,27 +392,23 @@ bool tune_skipped(int tile) {
 std::vector<GemmChoice> igemm_candidates(const IgemmArgs& a, size_t slab_bytes) {
   std::vector<GemmChoice> v;
   const long long cus = num_cus();
-  for (int t : {4, 1, 2, 8, 6, 3, 9, 7, 11, 12, 13, 14, 51, 52, 53, 54, 21, 22, 23, 24, 25, 26, 31, 32, 33, 34, 35,
-                36, 41, 42, 43, 44, 63, 65, 66, 67, 68, 81, 82, 83, 84, 85, 70, 71, 72, 73,
-                74, 75, 76, 77, 88, 91, 92, 93, 94, 95, 96, 97, 98, 99}) {  // fits() filters by precision and gather
-    if (!igemm_tile_fits(a, t) || tune_skipped(t)) continue;
-    // (86, the stream-K form of 85, and 87, the resident-weight 64-channel
-    // kernel, are forced only: measured slower on the shapes they target --
-    // DESIGN.md §13)
-    if (t == 86 && conv3_flat_sk_slab_bytes(a) > slab_bytes) continue;  // stream-K partial slots
-    v.push_back({t, 1});
-    if (t == 70 || t == 71 || t == 74)  // Winograd: no K split; the tile of its batched point GEMMs
-      for (int inner : {1, 2, 3, 4, 6, 7, 8, 9}) v.push_back({t, 100 + inner});
-    // Winograd (70-77) and the persistent ring 88 take no K split; the LDS-DMA
-    // rings 81-84 (3x3) and 91-99 (convT) do (the 24-48^2
-    // bottleneck grids give them 144-192 workgroups for 256 CUs)
-    if ((t >= 70 && t <= 77) || t == 88 || t == 86 || t == 87) continue;
-    const long long cnt = igemm_tile_count(a, t);
-    const long long slots = (long long)igemm_tile_slots(t) * cus;
+  for (const IgemmTile& t : igemm_tiles()) {  // fits() filters by precision and gather
+    // (forced-only tiles were measured slower on the shapes they target -- DESIGN.md §13)
+    if (!t.tuned || !igemm_tile_fits(a, t.id) || tune_skipped(t.id)) continue;
+    if (t.slab_bytes && t.slab_bytes(a) > slab_bytes) continue;
+    v.push_back({t.id, 1});
+    if (t.family == IgemmFamily::Wino)  // no K split; the tile of its batched point GEMMs
+      for (int inner : {1, 2, 3, 4, 6, 7, 8, 9}) v.push_back({t.id, 100 + inner});
+    // Winograd and the persistent ring take no K split; the LDS-DMA rings
+    // (3x3 and convT) do (the 24-48^2 bottleneck grids give
+    // them 144-192 workgroups for 256 CUs)
+    if (!t.ksplit) continue;
+    const long long cnt = igemm_tile_count(a, t.id);
+    const long long slots = (long long)t.slots * cus;
     if (cnt >= 4 * slots || a.N % 64 != 0) continue;  // enough workgroup rounds already
     for (int ks : {2, 3, 4, 6, 8}) {
       if (igemm_slab_bytes(a, ks) > slab_bytes || a.K / ks < 256 || cnt * ks > 8 * slots) break;
-      v.push_back({t, ks});
+      v.push_back({t.id, ks});
     }
   }
   return v;
@@ -423,45 +416,46 @@ std::vector<GemmChoice> igemm_candidates(const IgemmArgs& a, size_t slab_bytes) 
 
 std::vector<GemmChoice> wgrad_candidates(const WgradArgs& a) {
   std::vector<GemmChoice> v;
-  for (int t : {0, 1, 2, 3, 4, 10, 11, 12, 13, 14, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 40, 41, 42, 43, 44,
-                71, 74}) {  // fits() filters by precision
-    if (!wgrad_tile_fits(a, t) || tune_skipped(t)) continue;
-    if (t >= 40 && t <= 44) {  // convT LDS-DMA ring (one resident workgroup per CU): slab mode only
-      for (int per_cu : {11, 12}) v.push_back({t, per_cu});
-      continue;
+  for (const WgradTile& t : wgrad_tiles()) {  // fits() filters by precision
+    if (!wgrad_tile_fits(a, t.id) || tune_skipped(t.id)) continue;
+    auto add = [&](std::initializer_list<int> per_cus, int inner, bool slab) {
+      for (int per_cu : per_cus) v.push_back({t.id, encode(t, {per_cu, inner, slab})});
+    };
+    switch (t.family) {
+      case WgradFamily::RingT:  // convT LDS-DMA ring (one resident workgroup per CU): slab mode only
+        add({1, 2}, -1, true);
+        break;
+      case WgradFamily::Wino:  // point-GEMM tile (k_wgrad) x workgroups per CU
+        // (each pixel split adds a full points x Co x Ci slab by fp32 atomics:
+        // 1-2 per CU cut that traffic on the deep, few-tile layers); slab mode:
+        // plain-store partials, no accumulator memset
+        for (int inner : {0, 1, 2, 3, 4}) add({1, 2, 4, 8, 16}, inner, false);
+        if (a.slab)
+          for (int inner : {0, 3, 4}) add({1, 2, 4}, inner, true);
+        break;
+      case WgradFamily::Ring:  // LDS-DMA ring: one resident workgroup per CU
+        add({1, 2}, -1, false);
+        // slab mode: split partials by plain stores + one reduction pass
+        // instead of per-element fp32 atomics
+        if (a.slab) add({1, 2}, -1, true);
+        break;
+      case WgradFamily::Halo:  // workgroups per CU (the wide tiles: one resident, else two)
+        if (t.default_per_cu == 1) add({1, 2}, -1, false);
+        else add({1, 2, 4, 8}, -1, false);
+        break;
+      case WgradFamily::Column:
+        // pixel-split column tiles: fewer splits trade fill for fewer fp32
+        // atomics per output (the short-pixel convT weight gradients); slab
+        // mode: the same splits as plain-store partials + reduction
+        add({1, 2, 4, 8, 16}, -1, false);
+        if (a.slab && a.batch == 1) add({1, 2, 4}, -1, true);
+        break;
     }
-    if (t == 71 || t == 74) {  // Winograd: point-GEMM tile (k_wgrad 0-4) x workgroups per CU
-      // (each pixel split adds a full points x Co x Ci slab by fp32 atomics:
-      // 1-2 per CU cut that traffic on the deep, few-tile layers); + 1000:
-      // slab mode (plain-store partials, no accumulator memset)
-      for (int inner : {0, 1, 2, 3, 4})
-        for (int per_cu : {1, 2, 4, 8, 16}) v.push_back({t, per_cu + 100 * (inner + 1)});
-      if (a.slab)
-        for (int inner : {0, 3, 4})
-          for (int per_cu : {1, 2, 4}) v.push_back({t, 1000 + per_cu + 100 * (inner + 1)});
-      continue;
-    }
-    if (t >= 24 && t <= 33) {  // wide halo-tiled / LDS-DMA ring: one resident workgroup per CU
-      for (int per_cu : {1, 2}) v.push_back({t, per_cu});
-      // ring (26-33) in slab mode: split partials by plain stores + one
-      // reduction pass instead of per-element fp32 atomics
-      if (t >= 26 && a.slab)
-        for (int per_cu : {11, 12}) v.push_back({t, per_cu});
-      continue;
-    }
-    if (t >= 20) {  // halo-tiled: workgroups per CU (2 resident)
-      for (int per_cu : {1, 2, 4, 8}) v.push_back({t, per_cu});
-      continue;
-    }
-    // pixel-split column tiles: fewer splits trade fill for fewer fp32
-    // atomics per output (the short-pixel convT weight gradients); codes
-    // 101-104: the same splits in slab mode (plain-store partials + reduction)
-    for (int per_cu : {1, 2, 4, 8, 16}) v.push_back({t, per_cu});
-    if (a.slab && a.batch == 1)
-      for (int per_cu : {101, 102, 104}) v.push_back({t, per_cu});
   }
   return v;
 }
+}  // namespace unet
+namespace {
 
 // min over 2 timed runs after 1 warm-up; < 0 if the launch failed
 template <typename F>
@@ -504,9 +498,10 @@ GemmChoice choose_igemm(const Ctx& c, const IgemmArgs& a) {
     const int ks = unet::g_force_split > 1 ? unet::g_force_split : 1;
     if (igemm_slab_bytes(a, ks) > c.p->slab.bytes) return GemmChoice{};
     if (unet::g_force_tile > 0) {
-      if (igemm_tile_fits(a, unet::g_force_tile) &&
-          (unet::g_force_tile != 86 || (ks == 1 && conv3_flat_sk_slab_bytes(a) <= c.p->slab.bytes)))
-        return GemmChoice{unet::g_force_tile, ks};
+      const IgemmTile* ft = igemm_tile(unet::g_force_tile);
+      if (ft && igemm_tile_fits(a, ft->id) &&
+          (!ft->slab_bytes || (ks == 1 && ft->slab_bytes(a) <= c.p->slab.bytes)))
+        return GemmChoice{ft->id, ks};
     }
     for (int t : {4, 1, 2, 8, 21, 22, 24, 23})
       if (igemm_tile_fits(a, t)) return GemmChoice{t, ks};
@@ -522,8 +517,10 @@ GemmChoice choose_igemm(const Ctx& c, const IgemmArgs& a) {
     // database from another tile set, or a split whose partials no longer fit
     // the slab): otherwise it is dropped and the shape re-tuned
     const GemmChoice g = it->second;
-    const bool slab_ok = g.tile == 86 ? conv3_flat_sk_slab_bytes(a) <= c.p->slab.bytes
-                                      : g.tile >= 70 || igemm_slab_bytes(a, g.split) <= c.p->slab.bytes;  // Winograd: split = inner tile
+    const IgemmTile* t = igemm_tile(g.tile);
+    // (a tile without a K split: its split code is no slab size)
+    const bool slab_ok = t && (t->slab_bytes ? t->slab_bytes(a) : t->ksplit ? igemm_slab_bytes(a, g.split) : 0) <=
+                                  c.p->slab.bytes;
     if (g.tile < 0 || (igemm_tile_fits(a, g.tile) && slab_ok)) return g;
     g_tuned.erase(it);
     g_tune_log.erase(key);

@@ -5,6 +5,8 @@
 #include <cstddef>
 #include <cstdint>
 #include <atomic>
+#include <string>
+#include <vector>
 
 namespace unet {
 
@@ -114,8 +116,8 @@ extern std::atomic<long long> g_slab_fallbacks;
 // deterministic mode (unet_set_tuning("deterministic", 1), plan.hip): no fp32
 // atomics in any weight gradient; sites that had no such variant are counted
 extern int g_deterministic;
-extern int g_bnb_fuse;
-extern int g_wgrad_early_u;  // plan.hip: Winograd weight gradients' U issued before the layer's dY  // plan.hip: fp32 BN-backward apply fused with the F(6x6) dY transform
+extern int g_bnb_fuse;       // plan.hip: fp32 BN-backward apply fused with the F(6x6) dY transform
+extern int g_wgrad_early_u;  // plan.hip: Winograd weight gradients' U issued before the layer's dY
 extern std::atomic<long long> g_nondet_sites;
 
 struct WgradArgs {
@@ -160,56 +162,147 @@ struct WgradArgs {
   int abl = 0;
 };
 
-// ---------------- launchers (kernels.hip) ----------------
-// Variant of a GEMM launch.  igemm: tile id (1-4, 6-9 register-staged,
-// 11-14 LDS-DMA staged, 21-26 bf16 operands; see igemm.hip) and K
-// split; wgrad: tile id (0-4 fp32, 10-14 bf16) and target workgroups per CU of
-// the pixel split.
+// ---------------- GEMM launchers (igemm.hip and the family files) ----------------
+// Variant of a GEMM launch: a tile id of the igemm / wgrad tile table below and
+// a split code.  igemm: the K split (unfused Winograd tiles: 100 + the tile of
+// their point GEMMs); wgrad: the packed code WgradMode decodes.
 // tile < 0 = built-in heuristic.  Chosen per launch site by the plan's autotuner.
 struct GemmChoice {
   int tile = -1;
   int split = 1;
 };
-// Winograd F(2x2, 3x3) fp32 path (winograd.hip), tile id 70
+
+// One row per igemm kernel variant, defined beside its kernels by the file that
+// instantiates them (*_tile_rows()).  igemm.hip concatenates the rows into the
+// table: the autotuner tries them in table order, forced-only rows last.
+enum class IgemmFamily {
+  Reg,       // k_igemm, k_igemm_g, k_igemm_bf: generic gathers, bm x bn x bk
+  Halo,      // k_conv3_f32, k_conv3_bf, k_conv3p_bf: 3x3, th x tw pixel tiles
+  Conv3Dma,  // k_conv3_dma
+  Ring,      // k_conv3_ring
+  Flat,      // k_conv3_flat
+  C64,       // k_conv3_c64
+  GemmRing,  // k_gemm_ring (convT)
+  Wino,      // unfused Winograd: transforms + batched point GEMMs
+  WinoFused
+};
+struct IgemmTile {
+  int id;
+  IgemmFamily family;
+  // bm = pixels and bn = columns per workgroup, bk = the split-K unit; slots =
+  // resident workgroups per CU (min of the LDS and VGPR limits of the built kernels)
+  int bm, bn, bk, slots;
+  int th, tw, ch;  // pixel tile and channel chunk of the 3x3 families (else 0)
+  int wino_m;      // Winograd output tile F(m x m, 3x3), 0 = direct
+  bool bf16;       // packed B operand: bf16 `bh` (else fp32 `b`)
+  bool x3;         // has a split-operand (bf16x3) kernel
+  bool ksplit;     // takes a K split
+  bool tuned;      // the autotuner tries it (else forced / database only)
+  bool (*fits)(const IgemmArgs&, const IgemmTile&);
+  hipError_t (*go)(const IgemmArgs&, hipStream_t);
+  long long (*count)(const IgemmArgs&);    // workgroups of one K slice; nullptr: from the geometry
+  size_t (*slab_bytes)(const IgemmArgs&);  // extra split-K slab bytes the tile needs; nullptr: none
+};
+struct IgemmTileRows {
+  const IgemmTile* p;
+  int n;
+};
+template <int N>
+constexpr IgemmTileRows tile_rows(const IgemmTile (&r)[N]) { return {r, N}; }
+// a 3x3 family row: bm and bk follow from the pixel tile and the channel chunk
+constexpr IgemmTile conv3_tile(int id, IgemmFamily f, int th, int tw, int bn, int ch, int slots, bool bf16, bool x3,
+                               bool ksplit, bool (*fits)(const IgemmArgs&, const IgemmTile&),
+                               hipError_t (*go)(const IgemmArgs&, hipStream_t)) {
+  return {id, f, th * tw, bn, 9 * ch, slots, th, tw, ch, 0, bf16, x3, ksplit, true, fits, go, nullptr, nullptr};
+}
+IgemmTileRows igemm_bf16_tile_rows();         // igemm_bf16.hip
+IgemmTileRows conv3_dma_tile_rows();          // conv3_dma.hip
+IgemmTileRows conv3_ring_tile_rows();         // conv3_ring.hip
+IgemmTileRows conv3_ring_pt_tile_rows();      // conv3_ring_pt.hip
+IgemmTileRows conv3_ring_persistent_tile_rows();
+IgemmTileRows conv3_flat_tile_rows();         // conv3_flat.hip
+IgemmTileRows conv3_c64_tile_rows();          // conv3_c64.hip
+IgemmTileRows gemm_ring_tile_rows();          // gemm_ring.hip and its _p1 / _p2 units
+IgemmTileRows gemm_ring_p1_tile_rows();
+IgemmTileRows gemm_ring_p2_tile_rows();
+IgemmTileRows wino_tile_rows();               // winograd.hip
+const std::vector<IgemmTile>& igemm_tiles();  // the table
+const IgemmTile* igemm_tile(int id);          // nullptr: no such tile
+// packed B in the tile's precision (split operands only where a kernel exists)
+inline bool igemm_prec_ok(const IgemmArgs& a, const IgemmTile& t) {
+  return t.bf16 ? a.bh != nullptr && (a.bl == nullptr || t.x3) : a.b != nullptr;
+}
+
+// Weight-gradient tiles.  The family tells how GemmChoice::split is read:
+//   Column (pixel-column tiles, k_wgrad / k_wgrad_bf): per_cu, + 100 slab mode
+//   Halo (k_wgrad3_bf, k_wgrad3_f32, k_wgrad3w_bf): per_cu
+//   Ring (k_wgrad3_ring), RingT (k_wgradT_ring): per_cu, + 10 slab mode
+//   Wino: per_cu + 100 * (1 + point-GEMM tile), + 1000 slab mode
+// per_cu = target workgroups per CU of the pixel split; slab mode = split
+// partials by plain stores and one reduction pass instead of fp32 atomics.
+enum class WgradFamily { Column, Halo, Ring, RingT, Wino };
+struct WgradMode {
+  int per_cu;
+  int inner;   // Winograd: tile of the point GEMMs, -1 = heuristic
+  bool slab;
+};
+struct WgradTile {
+  int id;
+  WgradFamily family;
+  int bm, bn;      // output rows x columns per workgroup (Halo / Ring: co x ci)
+  int th, tw;      // pixel tile (Halo / Ring), else 0
+  int wino_m;
+  bool bf16;
+  int default_per_cu;
+  bool (*fits)(const WgradArgs&, const WgradTile&);
+  hipError_t (*go)(const WgradArgs&, hipStream_t, WgradMode);  // nullptr for Column tiles, which
+  hipError_t (*go_column)(const WgradArgs&, hipStream_t, dim3 grid);  // run on launch_wgrad_v's pixel-split grid
+};
+struct WgradTileRows {
+  const WgradTile* p;
+  int n;
+};
+template <int N>
+constexpr WgradTileRows tile_rows(const WgradTile (&r)[N]) { return {r, N}; }
+WgradTileRows wgrad_bf16_tile_rows();   // igemm_bf16.hip: k_wgrad_bf
+WgradTileRows wgrad3_bf16_tile_rows();  // igemm_bf16.hip: k_wgrad3_bf
+WgradTileRows wgrad3w_tile_rows();      // igemm_bf16.hip: k_wgrad3w_bf
+WgradTileRows wgrad3_ring_tile_rows();  // wgrad3_ring.hip
+WgradTileRows wgradT_ring_tile_rows();  // wgradT_ring.hip
+WgradTileRows wino_wgrad_tile_rows();   // winograd.hip
+const std::vector<WgradTile>& wgrad_tiles();
+const WgradTile* wgrad_tile(int id);
+WgradMode decode(const WgradTile& t, int code);
+int encode(const WgradTile& t, WgradMode m);
+// what the public knobs igemm_variant / wgrad_variant (g_tune_igemm / g_tune_wgrad)
+// force for this launch; tile < 0: nothing, the heuristic decides
+GemmChoice resolve_forced_igemm(const IgemmArgs& a, int knob);
+GemmChoice resolve_forced_wgrad(const WgradArgs& a, int knob);
+// Winograd fp32 paths (winograd.hip)
 size_t wino_ws_bytes(long long T, int Cg, int N);
 size_t wino_ws_bytes_grid(int nimg, int H, int W, int Cg, int N);
 bool wino_applies(const IgemmArgs& a, int mt);           // mt = 2: F(2x2, 3x3), 4: F(4x4, 3x3)
 hipError_t launch_wino(const IgemmArgs& a, hipStream_t s, int mt);
-bool wino_wgrad_applies(const WgradArgs& a, int mt);  // weight gradient, mt = 4 (wgrad tile 71) / 6 (74)
-bool wino_fused_applies(const IgemmArgs& a);  // tile 72: fused F(4x4, 3x3)
-bool wino_fused64_applies(const IgemmArgs& a);  // tile 73: fused F(4x4, 3x3), 64 output channels
-hipError_t launch_wino_fused(const IgemmArgs& a, hipStream_t s);
-hipError_t launch_wino_fused64(const IgemmArgs& a, hipStream_t s);
-bool wino_fused64p_applies(const IgemmArgs& a);  // tile 76: tile 73 on a software-pipelined chunk loop
-hipError_t launch_wino_fused64p(const IgemmArgs& a, hipStream_t s);
-// tiles 75 / 77: fused F(2x2, 3x3), nc = 64 / 32 output channels x 64 tiles per workgroup
-bool wino_fused2_applies(const IgemmArgs& a, int nc);
-hipError_t launch_wino_fused2(const IgemmArgs& a, hipStream_t s, int nc);
+bool wino_wgrad_applies(const WgradArgs& a, int mt);  // weight gradient, mt = 4 / 6
 // MFMA flops a GEMM launch executes with variant c (Winograd: 2 * points *
 // tiles * Cg * N; otherwise the direct 2 * M * N * K)
 double igemm_exec_flops(const IgemmArgs& a, GemmChoice c);
 double wgrad_exec_flops(const WgradArgs& a, GemmChoice c);
-hipError_t launch_wino_wgrad(const WgradArgs& a, hipStream_t s, int per_cu, int mt);
+hipError_t launch_wino_wgrad(const WgradArgs& a, hipStream_t s, WgradMode m, int mt);
+// 4 / 6: launch_wgrad_v(a, s, c) runs Winograd F(mt x mt); else 0
 int wgrad_winograd_mt(const WgradArgs& a, GemmChoice c);
-hipError_t launch_wino_wgrad_u(const WgradArgs& a, hipStream_t s, int mt);  // 4 / 6: the launch is Winograd F(mt x mt); else 0
+hipError_t launch_wino_wgrad_u(const WgradArgs& a, hipStream_t s, int mt);
 // fp32 BatchNorm-backward apply fused with the F(6x6) weight gradient's dY
 // transform: dYpad (pad 2, border zeroed) and Vd[64][T][c] in one pass
 size_t bnb_wino6_vd_bytes(int n, int h, int w, int c);
 hipError_t launch_bnb_wino6_dy(const float* dz, const float* y, const float* coef, int n, int h, int w, int c,
                                float* dypad, float* vd, hipStream_t s);
-// bf16 halo conv with LDS-DMA weights (conv3_dma.hip), tile ids 63 and 65-68
-bool conv3_dma_tile_shape(int tile, int& th, int& bn, int& ch);
-hipError_t go_conv3_dma_tile(const IgemmArgs& a, hipStream_t s, int tile);
-// bf16 3x3 conv with LDS-DMA halo / weight rings (conv3_ring.hip), tile ids 81-84
-// (88: the geometry of 84, persistent)
-bool conv3_ring_tile_shape(int tile, int& th, int& bn, int& ck);
-bool conv3_ring_fits(const IgemmArgs& a, int tile);
-hipError_t go_conv3_ring_tile(const IgemmArgs& a, hipStream_t s, int tile);
-hipError_t go_conv3_ring_pt(const IgemmArgs& a, hipStream_t s, int tile);  // conv3_ring_pt.hip (83, 84, 88)
-// bf16 convT forward / input gradient on LDS-DMA K rings (gemm_ring.hip), tile ids 91-99
-bool gemm_ring_tile_shape(int tile, int& bm, int& bn);
-bool gemm_ring_fits(const IgemmArgs& a, int tile);
-hipError_t go_gemm_ring_tile(const IgemmArgs& a, hipStream_t s, int tile);
+// bf16 3x3 conv with LDS-DMA halo / weight rings (conv3_ring.hip; its rows' fits)
+bool conv3_ring_fits(const IgemmArgs& a, const IgemmTile& t);
+// bf16 convT forward / input gradient on LDS-DMA K rings (gemm_ring.hip; its rows' fits)
+bool gemm_ring_fits(const IgemmArgs& a, const IgemmTile& t);
+// stream-K partial slots of the flat tile's stream-K form (conv3_flat.hip)
+size_t conv3_flat_sk_slab_bytes(const IgemmArgs& a);
 int num_cus();
 
 // Timing-ablation switches (UNET_WG_ABL, UNET_WF_ABL, UNET_WF64_ABL: kernel
@@ -220,39 +313,36 @@ int num_cus();
 int ablation_env(const char* name);
 hipError_t launch_igemm(const IgemmArgs& a, hipStream_t s);  // heuristic
 hipError_t launch_igemm_v(const IgemmArgs& a, hipStream_t s, GemmChoice c);
+int igemm_heuristic_tile(const IgemmArgs& a);  // the tile launch_igemm runs
 bool igemm_tile_fits(const IgemmArgs& a, int tile);
 // workgroups of one K slice and resident workgroups per CU for a tile
 long long igemm_tile_count(const IgemmArgs& a, int tile);
 int igemm_tile_slots(int tile);
 size_t igemm_slab_bytes(const IgemmArgs& a, int ksplit);
+// the tuner's side (plan.hip): keys of the tuning database, candidate variants
+// in the order they are timed, and whether a weight-gradient variant adds no
+// fp32 atomics
+std::string igemm_key(const IgemmArgs& a);
+std::string wgrad_key(const WgradArgs& a);
+std::vector<GemmChoice> igemm_candidates(const IgemmArgs& a, size_t slab_bytes);
+std::vector<GemmChoice> wgrad_candidates(const WgradArgs& a);
+bool wgrad_choice_deterministic(const GemmChoice& g);
 hipError_t launch_wgrad(const WgradArgs& a, hipStream_t s);  // heuristic
 hipError_t launch_wgrad_v(const WgradArgs& a, hipStream_t s, GemmChoice c);
 bool wgrad_tile_fits(const WgradArgs& a, int tile);
-// bf16-operand kernels (igemm_bf16.hip), dispatched by the launchers above
-hipError_t go_igemm_bf16(const IgemmArgs& a, hipStream_t s, int tile);
-// halo-tiled 3x3 tiles 31-36: output tile TH x TW pixels x BN columns
-bool halo_tile_shape(int tile, int& th, int& tw, int& bn);
-hipError_t go_wgrad_bf16(const WgradArgs& a, hipStream_t s, int tile, dim3 grid);
-// halo-tiled 3x3 weight gradient (wgrad tiles 20, 21): all 9 taps per workgroup
+// fits of the generic-gather and the halo families (igemm.hip)
+bool reg_tile_fits(const IgemmArgs& a, const IgemmTile& t);
+bool halo_tile_fits(const IgemmArgs& a, const IgemmTile& t);
+// halo-tiled 3x3 weight gradient (igemm_bf16.hip): all 9 taps per workgroup
 bool wgrad3_fits(const WgradArgs& a);
-hipError_t go_wgrad3_bf16(const WgradArgs& a, hipStream_t s, int tile, int per_cu);
-// 3x3 weight gradient with every operand staged by LDS-DMA through a 4-slot
-// ring of pixel tiles (wgrad tiles 26-33, wgrad3_ring.hip)
-bool wgrad3_ring_fits(const WgradArgs& a, int tile);
-hipError_t go_wgrad3_ring(const WgradArgs& a, hipStream_t s, int tile, int per_cu);
 // out[b][e] = sum_z slab[b * splits + z][e], e < plane (the slab-mode weight
 // gradients' reduction; out planes batch_out floats apart)
 hipError_t launch_slab_reduce(const float* slab, int splits, int batch, size_t plane, long long batch_out, float* out,
                               hipStream_t s);
 // pixel splits of a pixel-column weight-gradient tile (and the pixels per split)
-int wgrad_splits(const WgradArgs& a, int tile, int per_cu, int& pps);
+int wgrad_splits(const WgradArgs& a, const WgradTile& t, int per_cu, int& pps);
 // whether slab mode can hold `splits` partial planes (1 split: stores into out)
 bool wgrad_slab_fits(const WgradArgs& a, int splits);
-// wide halo-tiled 3x3 weight gradient with a two-stage ring (wgrad tiles 24, 25)
-bool wgrad3w_fits(const WgradArgs& a, int tile);
-hipError_t go_wgrad3w_bf16(const WgradArgs& a, hipStream_t s, int tile, int per_cu);
-// tiles 21-26 / 31-36 / 41-44 that have a split-operand kernel
-bool bf16_tile_splits(int tile);
 // out[i] = bf16(in[i]) (RNE), n a multiple of 4, in 16-B / out 8-B aligned;
 // lo (optional): lo[i] = bf16(in[i] - out[i]), the residual plane of split operands
 hipError_t launch_f2bf(const float* in, uint16_t* out, size_t n, hipStream_t s, uint16_t* lo = nullptr);

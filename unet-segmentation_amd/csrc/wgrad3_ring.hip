@@ -498,15 +498,10 @@ hipError_t launch_slab_reduce(const float* slab, int splits, int batch, size_t p
   return hipGetLastError();
 }
 
-// wgrad tiles 26-29 (igemm.hip wgrad_tile_fits / launch_wgrad_v):
-//   26: 128 co x 64 ci, 4 x 16 px tiles   27: 128 co x 64 ci, 8 x 8 px tiles
-//   28:  64 co x 64 ci, 4 x 16 px tiles   29:  64 co x 128 ci, 4 x 16 px tiles
-//   30:  64 co x 64 ci, 8 x 16 px tiles   31:  64 co x 64 ci, 8 x 8 px tiles
-//   32: slide, 128 co x 64 ci, 4 x 16 px  33: slide, 64 co x 128 ci, 4 x 16 px
-bool wgrad3_ring_fits(const WgradArgs& a, int tile) {
+static bool wgrad3_ring_fits(const WgradArgs& a, const WgradTile& t) {
   const Gather& g = a.gb;
-  const int bco = tile == 26 || tile == 27 || tile == 32 ? 128 : 64, bci = tile == 29 || tile == 33 ? 128 : 64;
-  if (tile < 26 || tile > 33 || !a.bf16 || a.split) return false;
+  const int bco = t.bm, bci = t.bn;
+  if (!a.bf16 || a.split) return false;
   const Src& d = a.ga.s[0];
   const bool two = g.c_split < g.Cg;
   // dY: the zero-bordered padded buffer (bf16); X sources bf16, with or without
@@ -522,14 +517,13 @@ bool wgrad3_ring_fits(const WgradArgs& a, int tile) {
 }
 
 template <int TH, int TW, int BCO, int BCI, int TMC>
-static hipError_t go_wr(const WgradArgs& a0, hipStream_t s, int per_cu) {
+static hipError_t go_wr(const WgradArgs& a0, hipStream_t s, WgradMode m) {
   using Gm = WRGeo<TH, TW, BCO, BCI>;
   static bool attr[2] = {false, false};
   const Gather& g = a0.gb;
-  // per_cu >= 10: slab mode (per_cu - 10 workgroups per CU), when the plan's
-  // slab holds every split's plane (else the atomics)
-  const bool slab_mode = per_cu >= 10;
-  if (slab_mode) per_cu -= 10;
+  // slab mode: when the plan's slab holds every split's plane (else the atomics)
+  const bool slab_mode = m.slab;
+  const int per_cu = m.per_cu;
   const int tiles = g.nimg * ((g.Hg + TH - 1) / TH) * ((g.Wg + TW - 1) / TW);
   const int blocks = (a0.Mo / BCO) * (g.Cg / BCI);
   int splits = (per_cu * num_cus() + blocks - 1) / blocks;
@@ -573,19 +567,17 @@ static hipError_t go_wr(const WgradArgs& a0, hipStream_t s, int per_cu) {
   return launch_slab_reduce(a.slab, splits, 1, plane, 0, a.out, s);
 }
 
-hipError_t go_wgrad3_ring(const WgradArgs& a, hipStream_t s, int tile, int per_cu) {
-  if (!wgrad3_ring_fits(a, tile)) return hipErrorInvalidValue;
-  switch (tile) {
-    case 26: return go_wr<4, 16, 128, 64, 2>(a, s, per_cu);
-    case 27: return go_wr<8, 8, 128, 64, 2>(a, s, per_cu);
-    case 28: return go_wr<4, 16, 64, 64, 1>(a, s, per_cu);
-    case 29: return go_wr<4, 16, 64, 128, 2>(a, s, per_cu);
-    case 30: return go_wr<8, 16, 64, 64, 1>(a, s, per_cu);
-    case 31: return go_wr<8, 8, 64, 64, 1>(a, s, per_cu);
-    case 32: return go_wr<4, 16, 128, 64, 0>(a, s, per_cu);
-    case 33: return go_wr<4, 16, 64, 128, 0>(a, s, per_cu);
-    default: return hipErrorInvalidValue;
-  }
+// TH x TW pixel tiles, BCO co x BCI ci per workgroup; TMC 0: the sliding form
+template <int TH, int TW, int BCO, int BCI, int TMC>
+static constexpr WgradTile wr_tile(int id) {
+  return {id, WgradFamily::Ring, BCO, BCI, TH, TW, 0, true, 1, wgrad3_ring_fits, &go_wr<TH, TW, BCO, BCI, TMC>, nullptr};
+}
+WgradTileRows wgrad3_ring_tile_rows() {
+  static const WgradTile rows[] = {wr_tile<4, 16, 128, 64, 2>(26), wr_tile<8, 8, 128, 64, 2>(27),
+                                   wr_tile<4, 16, 64, 64, 1>(28),  wr_tile<4, 16, 64, 128, 2>(29),
+                                   wr_tile<8, 16, 64, 64, 1>(30),  wr_tile<8, 8, 64, 64, 1>(31),
+                                   wr_tile<4, 16, 128, 64, 0>(32), wr_tile<4, 16, 64, 128, 0>(33)};
+  return tile_rows(rows);
 }
 
 }  // namespace unet

@@ -313,29 +313,11 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_wgradT_ring(const WgradArgs
 }
 
 // ---------------------------------------------------------------------------
-// tile ids (igemm.hip wgrad_tile_fits / launch_wgrad_v): BMO x BNO, BK pixels
-// per stage, NS stages
-//   40: 128 x 256, 8 waves (2 x 4, 64 x 64 each), BK 32, 6 stages: 144 KB
-//   41: 256 x 256, 8 waves (4 x 2, 64 x 128 each), BK 32, 4 stages: 128 KB
-//   42: 256 x 128, 8 waves (4 x 2, 64 x 64 each), BK 32, 6 stages: 144 KB
-//   43: 128 x 128, 8 waves (2 x 4, 64 x 32 each), BK 64, 4 stages: 128 KB
-//   44: 128 x 256, 8 waves (2 x 4, 64 x 64 each), BK 64, 3 stages: 144 KB
-// per_cu codes: >= 10 slab mode (per_cu - 10 workgroups per CU), else atomics
+// launcher and tile rows
 // ---------------------------------------------------------------------------
-static bool wgradT_shape(int tile, int& bmo, int& bno) {
-  switch (tile) {
-    case 40: bmo = 128; bno = 256; return true;
-    case 41: bmo = 256; bno = 256; return true;
-    case 42: bmo = 256; bno = 128; return true;
-    case 43: bmo = 128; bno = 128; return true;
-    case 44: bmo = 128; bno = 256; return true;
-    default: return false;
-  }
-}
-
-bool wgradT_ring_fits(const WgradArgs& a, int tile) {
-  int bmo, bno;
-  if (!wgradT_shape(tile, bmo, bno) || !a.bf16 || a.split || a.batch > 1) return false;
+static bool wgradT_ring_fits(const WgradArgs& a, const WgradTile& t) {
+  const int bmo = t.bm, bno = t.bn;
+  if (!a.bf16 || a.split || a.batch > 1) return false;
   const Gather& ga = a.ga;
   const Gather& gb = a.gb;
   const Src& xs = ga.s[0];
@@ -352,12 +334,11 @@ bool wgradT_ring_fits(const WgradArgs& a, int tile) {
 }
 
 template <int BMO, int BNO, int WM, int WN, int BK, int NS>
-static hipError_t go_wt(const WgradArgs& a0, hipStream_t s, int per_cu) {
+static hipError_t go_wt(const WgradArgs& a0, hipStream_t s, WgradMode m) {
   using G = WTGeo<BMO, BNO, BK, NS>;
   static bool attr[2] = {false, false};
-  const bool slab_mode = per_cu >= 10;
-  if (slab_mode) per_cu -= 10;
-  if (per_cu < 1) per_cu = 1;
+  const bool slab_mode = m.slab;
+  const int per_cu = m.per_cu < 1 ? 1 : m.per_cu;
   const int tm = a0.Mo / BMO, tn = a0.No / BNO, tiles = tm * tn;
   int splits = (per_cu * num_cus() + tiles - 1) / tiles;
   const int max_splits = (a0.P + BK - 1) / BK;
@@ -395,16 +376,18 @@ static hipError_t go_wt(const WgradArgs& a0, hipStream_t s, int per_cu) {
   return launch_slab_reduce(a.slab, splits, 1, plane, 0, a.out, s);
 }
 
-hipError_t go_wgradT_ring(const WgradArgs& a, hipStream_t s, int tile, int per_cu) {
-  if (!wgradT_ring_fits(a, tile)) return hipErrorInvalidValue;
-  switch (tile) {
-    case 40: return go_wt<128, 256, 2, 4, 32, 6>(a, s, per_cu);
-    case 41: return go_wt<256, 256, 4, 2, 32, 4>(a, s, per_cu);
-    case 42: return go_wt<256, 128, 4, 2, 32, 6>(a, s, per_cu);
-    case 43: return go_wt<128, 128, 2, 4, 64, 4>(a, s, per_cu);
-    case 44: return go_wt<128, 256, 2, 4, 64, 3>(a, s, per_cu);
-    default: return hipErrorInvalidValue;
-  }
+// BMO x BNO per workgroup on WM x WN waves, BK pixels per stage, NS stages
+template <int BMO, int BNO, int WM, int WN, int BK, int NS>
+static constexpr WgradTile wt_tile(int id) {
+  return {id, WgradFamily::RingT, BMO, BNO, 0, 0, 0, true, 1, wgradT_ring_fits, &go_wt<BMO, BNO, WM, WN, BK, NS>, nullptr};
+}
+WgradTileRows wgradT_ring_tile_rows() {
+  static const WgradTile rows[] = {wt_tile<128, 256, 2, 4, 32, 6>(40),   // 64 x 64 per wave; 144 KB
+                                   wt_tile<256, 256, 4, 2, 32, 4>(41),   // 64 x 128 per wave; 128 KB
+                                   wt_tile<256, 128, 4, 2, 32, 6>(42),   // 64 x 64 per wave; 144 KB
+                                   wt_tile<128, 128, 2, 4, 64, 4>(43),   // 64 x 32 per wave; 128 KB
+                                   wt_tile<128, 256, 2, 4, 64, 3>(44)};  // 64 x 64 per wave; 144 KB
+  return tile_rows(rows);
 }
 
 }  // namespace unet

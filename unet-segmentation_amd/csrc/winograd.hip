@@ -2426,16 +2426,11 @@ hipError_t launch_wino_wgrad_u(const WgradArgs& a, hipStream_t s, int mt) {
   return hipGetLastError();
 }
 
-// mt = 4 (wgrad tile 71) or 6 (tile 74).  per_cu: workgroups per CU of the point
-// GEMMs' pixel split, + 100 * (1 + k_wgrad tile id) to force their tile
-// (autotuner candidates)
-hipError_t launch_wino_wgrad(const WgradArgs& a, hipStream_t s, int per_cu, int mt) {
-  // code = [1000: slab mode] + [100 * (point-GEMM tile + 1)] + workgroups per CU
-  const bool slab = per_cu >= 1000;
-  per_cu %= 1000;
-  const int forced = per_cu >= 100 ? per_cu / 100 - 1 : -1;
-  per_cu %= 100;
-  if (per_cu <= 0) per_cu = 8;
+// mt = 4 or 6.  m: workgroups per CU of the point GEMMs' pixel split, their
+// tile (m.inner; -1: by shape) and slab mode (autotuner candidates)
+hipError_t launch_wino_wgrad(const WgradArgs& a, hipStream_t s, WgradMode m, int mt) {
+  const bool slab = m.slab;
+  const int forced = m.inner, per_cu = m.per_cu;
   if ((mt != 4 && mt != 6) || !wino_wgrad_applies(a, mt)) return hipErrorInvalidValue;
   const Gather& gb = a.gb;
   const int P = (mt + 2) * (mt + 2);
@@ -2499,10 +2494,11 @@ hipError_t launch_wino_wgrad(const WgradArgs& a, hipStream_t s, int per_cu, int 
     q.slab = a.slab;
     q.slab_bytes = a.slab_bytes;
     int pps = 0;
-    const bool use_slab = slab && wgrad_slab_fits(q, wgrad_splits(q, tile, per_cu, pps));
+    const WgradTile& pt = *wgrad_tile(tile);
+    const bool use_slab = slab && wgrad_slab_fits(q, wgrad_splits(q, pt, per_cu, pps));
     if (slab && !use_slab) ++g_slab_fallbacks;
     if (!use_slab && (e = hipMemsetAsync(Mw, 0, (size_t)P * Co * Ci * 4, s)) != hipSuccess) return e;
-    if ((e = launch_wgrad_v(q, s, GemmChoice{tile, use_slab ? per_cu + 100 : per_cu})) != hipSuccess) return e;
+    if ((e = launch_wgrad_v(q, s, GemmChoice{tile, encode(pt, {per_cu, -1, use_slab})})) != hipSuccess) return e;
   }
   const long long no = (long long)Co * Ci;
   if (mt == 4)
@@ -2510,6 +2506,59 @@ hipError_t launch_wino_wgrad(const WgradArgs& a, hipStream_t s, int per_cu, int 
   else
     hipLaunchKernelGGL(k_wino6_wout, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, s, Mw, Co, Ci, a.out);
   return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Tile rows.  bm x bn = output tiles (unfused: pixels) x channels per workgroup;
+// no K split (the unfused tiles' split code names the tile of their point GEMMs).
+// ---------------------------------------------------------------------------
+template <int MT>  // transforms + batched point GEMMs
+static constexpr IgemmTile wino_tile(int id) {
+  return {id, IgemmFamily::Wino, 256, 64, 9, 2, 0, 0, 0, MT, false, false, false, true,
+          [](const IgemmArgs& a, const IgemmTile&) { return wino_applies(a, MT); },
+          [](const IgemmArgs& a, hipStream_t s) { return launch_wino(a, s, MT); }, nullptr, nullptr};
+}
+static constexpr IgemmTile wino_fused_tile(int id, int mt, int bm, int bn, int bk, int slots,
+                                           bool (*fits)(const IgemmArgs&, const IgemmTile&),
+                                           hipError_t (*go)(const IgemmArgs&, hipStream_t)) {
+  return {id, IgemmFamily::WinoFused, bm, bn, bk, slots, 0, 0, 0, mt, false, false, false, true, fits, go, nullptr, nullptr};
+}
+template <int NC>  // fused F(2x2, 3x3), NC output channels x 64 tiles per workgroup
+static constexpr IgemmTile wino_fused2_tile(int id, int slots) {
+  return wino_fused_tile(id, 2, 64, NC, 8, slots,
+                         [](const IgemmArgs& a, const IgemmTile&) { return wino_fused2_applies(a, NC); },
+                         [](const IgemmArgs& a, hipStream_t s) { return launch_wino_fused2(a, s, NC); });
+}
+IgemmTileRows wino_tile_rows() {
+  static const IgemmTile rows[] = {
+      wino_tile<2>(70),
+      wino_tile<4>(71),
+      // fused F(4x4, 3x3): 32 tiles x 32 channels, 16-channel chunks
+      wino_fused_tile(72, 4, 32, 32, 16, 1, [](const IgemmArgs& a, const IgemmTile&) { return wino_fused_applies(a); },
+                      &launch_wino_fused),
+      // ... x 64 output channels, 8-channel chunks
+      wino_fused_tile(73, 4, 32, 64, 8, 1, [](const IgemmArgs& a, const IgemmTile&) { return wino_fused64_applies(a); },
+                      &launch_wino_fused64),
+      wino_tile<6>(74),
+      wino_fused2_tile<64>(75, 1),
+      // the 64-channel fused F(4x4) on a software-pipelined chunk loop
+      wino_fused_tile(76, 4, 32, 64, 8, 1, [](const IgemmArgs& a, const IgemmTile&) { return wino_fused64p_applies(a); },
+                      &launch_wino_fused64p),
+      wino_fused2_tile<32>(77, 2),
+  };
+  return tile_rows(rows);
+}
+
+// the Winograd weight gradients assign G^T Mw G to out: no accumulation
+template <int MT>
+static constexpr WgradTile wino_wgrad_tile(int id) {
+  return {id, WgradFamily::Wino, 0, 0, 0, 0, MT, false, 8,
+          [](const WgradArgs& a, const WgradTile&) { return !a.accumulate && wino_wgrad_applies(a, MT); },
+          [](const WgradArgs& a, hipStream_t s, WgradMode m) { return launch_wino_wgrad(a, s, m, MT); }, nullptr};
+}
+WgradTileRows wino_wgrad_tile_rows() {
+  static const WgradTile rows[] = {wino_wgrad_tile<4>(71), wino_wgrad_tile<6>(74)};
+  return tile_rows(rows);
 }
 
 }  // namespace unet
