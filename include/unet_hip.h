@@ -219,6 +219,15 @@ size_t unet_elastic_ws_bytes(int n, int h, int w);
 int unet_elastic_deform(const uint8_t* image, const uint16_t* labels, int n, int h, int w,
                         const double* noise, double alpha, double sigma, float* x_out,
                         uint8_t* target_out, uint8_t* image_out, void* ws, unet_stream_t stream);
+/* The same with the warped instance map: ids_out (n, h, w) uint16 (may be
+ * NULL) holds, at each output pixel, the id at the nearest source pixel the
+ * target was sampled from, and 0 wherever target_out is 0 (the reference's
+ * uint8 cast makes id 256 background; ids_out agrees with the target).
+ * unet_elastic_deform is this call with ids_out = NULL. */
+int unet_elastic_deform_ex(const uint8_t* image, const uint16_t* labels, int n, int h, int w,
+                           const double* noise, double alpha, double sigma, float* x_out,
+                           uint8_t* target_out, uint8_t* image_out, uint16_t* ids_out, void* ws,
+                           unet_stream_t stream);
 
 /* Overlap-tile inference (scripts/predict1.py:35-49
  * margin rule): tile t of an nx-wide tile grid has its input origin at
@@ -246,6 +255,25 @@ int unet_tile_scatter(const float* tile_logits, int k, int tile_out, int nx, int
 size_t unet_weight_map_ws_bytes(int n);
 int unet_weight_map(const uint16_t* labels, int n, int h, int w, double w0, double sigma, float* weights,
                     double* weights64, void* ws, unet_stream_t stream);
+
+/* Border-aware loss weight maps: the formula above with the U-Net paper's
+ * distances instead of the reference's zeros.  For each object l (a distinct
+ * non-zero id of a sample) dist_l(p) is the Euclidean distance from pixel p to
+ * the nearest pixel of l (0 inside l; scipy's distance_transform_edt(L != l)).
+ * d1 <= d2 are the two smallest dist_l(p) over the objects; with one object
+ * d2 = 0, with none d1 = d2 = 0 (preprocess_data.py:56-64).  Squared distances
+ * are exact int32; d = sqrt((double)d^2) is formed only for the exponential.
+ *   weights64 = (double)(float)wc + w0 * exp(-(d1 + d2)^2 / (2 (sigma^2 + 1e-8)))
+ *   weights   = (float)weights64
+ * weights64, d1sq, d2sq (n, h, w) may be NULL.  Cost and workspace do not
+ * depend on the number of objects or on the id values; no host
+ * synchronisation; bit-reproducible.  n, h, w >= 1 and h, w <= 16384 (h^2 + w^2
+ * must fit int32), else -EINVAL before any launch and a workspace size of 0.
+ * ws >= unet_weight_map_border_ws_bytes(n, h, w) (16 B per pixel + counts),
+ * 16-byte aligned. */
+size_t unet_weight_map_border_ws_bytes(int n, int h, int w);
+int unet_weight_map_border(const uint16_t* labels, int n, int h, int w, double w0, double sigma, float* weights,
+                           double* weights64, int32_t* d1sq, int32_t* d2sq, void* ws, unet_stream_t stream);
 
 /* Post-processing (utils/metrics.py):
  * unet_instance_masks: get_instance_masks (:42-72) for n masks (h, w) uint8

@@ -1,5 +1,6 @@
 """Throughput of the widened §8f rows next to their CPU restatements, one JSON
-line each: loss weight maps (unet_weight_map), instance masks (8-connected
+line each: loss weight maps (unet_weight_map), border-aware weight maps
+(unet_weight_map_border, the 3 HeLa frames), instance masks (8-connected
 labelling + small-object removal, unet_instance_masks) and the Rand index
 (unet_rand_index), on the real HeLa masks tiled up to the training batch
 (8 x 512 x 512 label maps / 324 x 324 predicted masks).
@@ -7,7 +8,9 @@ labelling + small-object removal, unet_instance_masks) and the Rand index
     python tools/aux_bench.py [--iters 50]
 
 HBM bytes per launch (algorithmic): weight maps 2 B read + 4 B written per
-pixel (+ a 2-B count pass); instance masks 1 B read, 4 x 4 B work arrays
+pixel (+ a 2-B count pass); border maps 2 B read + 16 B of candidates written
+and read (per 256-column tile of the row) + 4 B written per pixel, but bound
+by the row sweep's integer VALU work (4 w candidates per pixel); instance masks 1 B read, 4 x 4 B work arrays
 written and read, 2 B written per pixel; Rand index 2 x 2 B read per pixel
 (twice: presence marks, histogram).
 """
@@ -69,6 +72,30 @@ def main():
                                    "peak_gbs": 8000.0},
                       "cpu_baseline": {"value": round(1e3 / cpu, 1), "unit": "maps/s", "cores": 1, "kind": "port",
                                        "sample": "3 maps 512x512, oracle/weightmap_oracle.py"}}))
+    # border-aware maps: the three HeLa frames in one batch; the CPU restatement
+    # (one scipy EDT per object) only where scipy imports
+    d3 = torch.from_numpy(z["segs"]).cuda()
+    ms = gpu_time(lambda: weight_maps(d3, mode="border"), args.iters)
+    line = {"metric": "border weight maps/s (unet_weight_map_border)", "value": round(3 / (ms * 1e-3), 1),
+            "unit": "maps/s", "ms_per_batch": round(ms, 4), "ms_per_map": round(ms / 3, 4),
+            "config": {"batch": 3, "size": 512, "objects": int(len(np.unique(z["segs"][0])) - 1)},
+            # nominal: 4 w candidates per pixel, before the sweep's early exit skips the far ones
+            "roofline": {"bound": "int32 VALU (row sweep: up to 4 w candidates per pixel)",
+                         "nominal_candidate_updates_per_s": round(d3.numel() * 512 * 4 / (ms * 1e-3), 0)}}
+    try:
+        from scipy.ndimage import distance_transform_edt
+
+        def scipy_map(lab):
+            sq = np.stack([distance_transform_edt(lab != l) for l in np.unique(lab[lab > 0])], -1)
+            d = np.partition(sq, 1, axis=-1)[..., :2].sum(-1)
+            return 10.0 * np.exp(-d ** 2 / (2 * (5.0 ** 2 + 1e-8)))
+        cpu = cpu_time(lambda: scipy_map(z["segs"][0]), 2)
+        line["cpu_baseline"] = {"value": round(1e3 / cpu, 2), "unit": "maps/s", "ms_per_map": round(cpu, 1),
+                                "cores": 1, "kind": "restatement",
+                                "sample": "2 runs of frame 0, one scipy distance_transform_edt per object"}
+    except ImportError:
+        pass
+    print(json.dumps(line))
     ms = gpu_time(lambda: instance_masks(dmasks, 15), args.iters)
     cpu = cpu_time(lambda: P.get_instance_masks(masks[0], 15), 1)
     px = masks.size

@@ -47,7 +47,7 @@ def load_frames(args):
     return np.stack(imgs), np.stack(labs)
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data", default=None)
     ap.add_argument("--seq", default="01")
@@ -57,10 +57,15 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--val", type=float, default=0.1)
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "bf16x3"])
-    ap.add_argument("--weights", default="static", choices=["static", "warped"])
+    ap.add_argument("--weights", default="static", choices=["static", "warped", "border", "border-warped"])
     ap.add_argument("--no-augment", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--checkpoint", default=None, help="save the best-val state_dict here")
+    return ap
+
+
+def main():
+    ap = build_parser()
     args = ap.parse_args()
     if not (args.data or args.npz):
         ap.error("--data or --npz")

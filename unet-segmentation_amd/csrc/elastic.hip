@@ -108,7 +108,7 @@ __device__ __forceinline__ unsigned to_uint(double v, double hi) {
 __global__ __launch_bounds__(256) void k_warp(const uint8_t* __restrict__ img, const uint16_t* __restrict__ lab,
                                               const double* __restrict__ d, int n, int h, int w,
                                               float* __restrict__ xo, uint8_t* __restrict__ to,
-                                              uint8_t* __restrict__ io) {
+                                              uint8_t* __restrict__ io, uint16_t* __restrict__ ido) {
   const size_t hw = (size_t)h * w;
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i >= (size_t)n * hw) return;
@@ -130,10 +130,12 @@ __global__ __launch_bounds__(256) void k_warp(const uint8_t* __restrict__ img, c
   const unsigned iv = to_uint(v, 255.0);
   // order 0 (labels): nearest, round half up; the uint16 -> uint8 cast wraps
   const int ny = reflect_index((int)floor(cy + 0.5), h), nx = reflect_index((int)floor(cx + 0.5), w);
-  const unsigned lv = lb[ny * w + nx] & 0xffu;
+  const unsigned id = lb[ny * w + nx];
+  const unsigned lv = id & 0xffu;
   xo[i] = (float)iv / 255.0f;
   to[i] = lv != 0 ? 1 : 0;
   if (io) io[i] = (uint8_t)iv;
+  if (ido) ido[i] = lv != 0 ? (uint16_t)id : 0;  // the warped instance map; background where the target is
 }
 
 static int gauss_radius(double sigma) { return (int)(4.0 * sigma + 0.5); }
@@ -141,8 +143,8 @@ static int gauss_radius(double sigma) { return (int)(4.0 * sigma + 0.5); }
 size_t elastic_ws_bytes(int n, int h, int w) { return (size_t)2 * (2 * (size_t)n * h * w) * sizeof(double); }
 
 hipError_t launch_elastic(const uint8_t* img, const uint16_t* lab, int n, int h, int w, const double* noise,
-                          double alpha, double sigma, float* x_out, uint8_t* t_out, uint8_t* img_out, void* ws,
-                          hipStream_t s) {
+                          double alpha, double sigma, float* x_out, uint8_t* t_out, uint8_t* img_out, uint16_t* ids_out,
+                          void* ws, hipStream_t s) {
   const int r = gauss_radius(sigma);
   if (n < 1 || h < 1 || w < 1 || !(sigma > 0) || r < 0 || 2 * r + 1 > kGaussMaxTaps) return hipErrorInvalidValue;
   // kernel weights exactly as oracle/elastic_oracle.py gaussian_kernel (fp64, normalised by the sum)
@@ -175,7 +177,7 @@ hipError_t launch_elastic(const uint8_t* img, const uint16_t* lab, int n, int h,
                      alpha);
   const size_t total = (size_t)n * h * w;
   hipLaunchKernelGGL(k_warp, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, img, lab, disp, n, h, w, x_out,
-                     t_out, img_out);
+                     t_out, img_out, ids_out);
   return hipGetLastError();
 }
 

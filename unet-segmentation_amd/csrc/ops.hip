@@ -601,15 +601,43 @@ int unet_weight_map(const uint16_t* labels, int n, int h, int w, double w0, doub
   return 0;
 }
 
+size_t unet_weight_map_border_ws_bytes(int n, int h, int w) { return weight_map_border_ws_bytes(n, h, w); }
+
+int unet_weight_map_border(const uint16_t* labels, int n, int h, int w, double w0, double sigma, float* weights,
+                           double* weights64, int32_t* d1sq, int32_t* d2sq, void* ws, unet_stream_t st) {
+  if (n < 1 || h < 1 || w < 1 || h > 16384 || w > 16384) {
+    set_last_error("unet_weight_map_border: need n, h, w >= 1 and h, w <= 16384 (h^2 + w^2 must fit int32)");
+    return -EINVAL;
+  }
+  if (!labels || !weights || !ws || (reinterpret_cast<uintptr_t>(ws) & 15)) {
+    set_last_error("unet_weight_map_border: null labels / weights / ws, or ws not 16-byte aligned");
+    return -EINVAL;
+  }
+  const hipError_t e = launch_weight_map_border(labels, n, h, w, w0, sigma, weights, weights64, d1sq, d2sq, ws,
+                                                reinterpret_cast<hipStream_t>(st));
+  if (e != hipSuccess) {
+    set_last_error(std::string("unet_weight_map_border: ") + hipGetErrorString(e));
+    return e == hipErrorInvalidValue ? -EINVAL : -EIO;
+  }
+  return 0;
+}
+
 size_t unet_elastic_ws_bytes(int n, int h, int w) { return n > 0 && h > 0 && w > 0 ? elastic_ws_bytes(n, h, w) : 0; }
+
+int unet_elastic_deform_ex(const uint8_t* image, const uint16_t* labels, int n, int h, int w, const double* noise,
+                           double alpha, double sigma, float* x_out, uint8_t* target_out, uint8_t* image_out,
+                           uint16_t* ids_out, void* ws, unet_stream_t st) {
+  if (!image || !labels || !noise || !x_out || !target_out || !ws || (reinterpret_cast<uintptr_t>(ws) & 7)) return -EINVAL;
+  OPCK(launch_elastic(image, labels, n, h, w, noise, alpha, sigma, x_out, target_out, image_out, ids_out, ws,
+                      reinterpret_cast<hipStream_t>(st)));
+  return 0;
+}
 
 int unet_elastic_deform(const uint8_t* image, const uint16_t* labels, int n, int h, int w, const double* noise,
                         double alpha, double sigma, float* x_out, uint8_t* target_out, uint8_t* image_out, void* ws,
                         unet_stream_t st) {
-  if (!image || !labels || !noise || !x_out || !target_out || !ws || (reinterpret_cast<uintptr_t>(ws) & 7)) return -EINVAL;
-  OPCK(launch_elastic(image, labels, n, h, w, noise, alpha, sigma, x_out, target_out, image_out, ws,
-                      reinterpret_cast<hipStream_t>(st)));
-  return 0;
+  return unet_elastic_deform_ex(image, labels, n, h, w, noise, alpha, sigma, x_out, target_out, image_out, nullptr, ws,
+                                st);
 }
 
 int unet_mask_from_logits(const float* logits, uint8_t* mask, int n, int h, int w, unet_stream_t st) {

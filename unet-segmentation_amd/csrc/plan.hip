@@ -88,6 +88,13 @@ namespace {
 
 thread_local std::string g_err;
 void set_err(const std::string& s) { g_err = s; }
+}  // namespace
+
+namespace unet {
+void set_last_error(const std::string& s) { set_err(s); }
+}  // namespace unet
+
+namespace {
 
 constexpr float kEps = 1e-5f, kMom = 0.1f;
 

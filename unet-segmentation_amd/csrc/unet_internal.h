@@ -361,16 +361,22 @@ size_t rand_index_ws_bytes(int h, int w);
 hipError_t launch_rand_index(const uint16_t* g, const uint16_t* p, int h, int w, double* out, void* ws,
                              hipStream_t s);
 
+// the text unet_last_error() returns on the calling thread (plan.hip)
+void set_last_error(const std::string& s);
+
 // loss weight maps (weightmap.hip)
 size_t weight_map_ws_bytes(int n);
 hipError_t launch_weight_map(const uint16_t* lab, int n, int h, int w, double w0, double sigma, float* out,
                              double* out64, void* ws, hipStream_t s);
+size_t weight_map_border_ws_bytes(int n, int h, int w);  // 0 for n, h, w < 1 or h, w > 16384
+hipError_t launch_weight_map_border(const uint16_t* lab, int n, int h, int w, double w0, double sigma, float* out,
+                                    double* out64, int32_t* d1sq, int32_t* d2sq, void* ws, hipStream_t s);
 
 // elastic-deformation input pipeline (elastic.hip)
 size_t elastic_ws_bytes(int n, int h, int w);
 hipError_t launch_elastic(const uint8_t* img, const uint16_t* lab, int n, int h, int w, const double* noise,
-                          double alpha, double sigma, float* x_out, uint8_t* t_out, uint8_t* img_out, void* ws,
-                          hipStream_t s);
+                          double alpha, double sigma, float* x_out, uint8_t* t_out, uint8_t* img_out, uint16_t* ids_out,
+                          void* ws, hipStream_t s);
 
 // inc.c0: Ci in {1,2,3,4} direct conv from an NCHW input; y NHWC (Co = 64 multiple).
 hipError_t launch_conv_first_fwd(const float* x_nchw, int n, int ci, int h, int w,

@@ -57,9 +57,13 @@ SIGNATURES = {
     "unet_rand_index": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "unet_weight_map_ws_bytes": (_sz, [_i]),
     "unet_weight_map": (_i, [_vp, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp]),
+    "unet_weight_map_border_ws_bytes": (_sz, [_i, _i, _i]),
+    "unet_weight_map_border": (_i, [_vp, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "unet_elastic_ws_bytes": (_sz, [_i, _i, _i]),
     "unet_elastic_deform": (_i, [_vp, _vp, _i, _i, _i, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp,
                                  _vp]),
+    "unet_elastic_deform_ex": (_i, [_vp, _vp, _i, _i, _i, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp,
+                                    _vp, _vp]),
     "unet_conv3x3_fwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "unet_conv3x3_dgrad": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "unet_conv3x3_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

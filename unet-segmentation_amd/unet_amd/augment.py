@@ -53,9 +53,11 @@ class ElasticDeform:
         return torch.rand((n, 2, h, w), dtype=torch.float64, device=device, generator=self.generator)
 
     def __call__(self, images: torch.Tensor, labels: torch.Tensor, seeds=None, noise: torch.Tensor | None = None,
-                 return_image: bool = False):
+                 return_image: bool = False, return_ids: bool = False):
         """images (N, H, W) uint8, labels (N, H, W) uint16 (instance ids; the
-        reference casts them to uint8 before `> 0`), both on the HIP device."""
+        reference casts them to uint8 before `> 0`), both on the HIP device.
+        return_ids appends the warped instance map (N, H, W) uint16: the id at
+        the source pixel the target was sampled from, 0 where the target is 0."""
         if images.device.type != "cuda" or labels.device.type != "cuda":
             raise ValueError("ElasticDeform runs on the HIP device only (no CPU fallback)")
         if images.dtype != torch.uint8 or images.dim() != 3:
@@ -77,18 +79,33 @@ class ElasticDeform:
         x = torch.empty((n, 1, h, w), dtype=torch.float32, device=images.device)
         t = torch.empty((n, 1, h, w), dtype=torch.uint8, device=images.device)
         img = torch.empty((n, h, w), dtype=torch.uint8, device=images.device) if return_image else None
-        _lib.check(self.lib.unet_elastic_deform(images.data_ptr(), labels.data_ptr(), n, h, w, noise.data_ptr(),
-                                                ctypes.c_double(self.alpha), ctypes.c_double(self.sigma),
-                                                x.data_ptr(), t.data_ptr(), img.data_ptr() if img is not None else None,
-                                                self._ws.data_ptr(), _lib.stream_of()), "unet_elastic_deform")
-        return (x, t, img) if return_image else (x, t)
+        ids = torch.empty((n, h, w), dtype=torch.uint16, device=images.device) if return_ids else None
+        _lib.check(self.lib.unet_elastic_deform_ex(images.data_ptr(), labels.data_ptr(), n, h, w, noise.data_ptr(),
+                                                   ctypes.c_double(self.alpha), ctypes.c_double(self.sigma),
+                                                   x.data_ptr(), t.data_ptr(), _lib.ptr(img), _lib.ptr(ids),
+                                                   self._ws.data_ptr(), _lib.stream_of()), "unet_elastic_deform_ex")
+        out = (x, t, img) if return_image else (x, t)
+        return out + (ids,) if return_ids else out
 
 
-def weight_maps(labels: torch.Tensor, w0: float = 10.0, sigma: float = 5.0, fp64: bool = False):
+WEIGHT_MAP_MODES = ("reference", "border")
+
+
+def weight_maps(labels: torch.Tensor, w0: float = 10.0, sigma: float = 5.0, fp64: bool = False,
+                mode: str = "reference", return_distances: bool = False):
     """scripts/preprocess_data.py:17-77 on the device for a batch of label maps
     (N, H, W) (uint16 instance ids, or any integer type): the per-pixel loss
     weights (N, H, W) fp32 utils/dataset.py:111 feeds the loss, and with
-    fp64=True also the fp64 map the reference saves as weight_map_*.npy."""
+    fp64=True also the fp64 map the reference saves as weight_map_*.npy.
+
+    mode="reference" is what the reference computes (its distances are
+    identically zero: a per-class constant).  mode="border" is the U-Net
+    paper's term, with d1 and d2 the exact Euclidean distances to the nearest
+    and second-nearest object (unet_weight_map_border); return_distances=True
+    appends their squares (d1sq, d2sq), (N, H, W) int32 (zeros in reference
+    mode, as in the reference)."""
+    if mode not in WEIGHT_MAP_MODES:
+        raise ValueError(f"mode must be one of {WEIGHT_MAP_MODES}, got {mode!r}")
     lib = _lib.load()
     if labels.device.type != "cuda" or labels.dim() != 3:
         raise ValueError("labels must be an (N, H, W) tensor on the HIP device")
@@ -98,8 +115,27 @@ def weight_maps(labels: torch.Tensor, w0: float = 10.0, sigma: float = 5.0, fp64
     n, h, w = labels.shape
     out = torch.empty((n, h, w), dtype=torch.float32, device=labels.device)
     out64 = torch.empty((n, h, w), dtype=torch.float64, device=labels.device) if fp64 else None
-    ws = torch.empty(lib.unet_weight_map_ws_bytes(n), dtype=torch.uint8, device=labels.device)
-    _lib.check(lib.unet_weight_map(labels.data_ptr(), n, h, w, ctypes.c_double(w0), ctypes.c_double(sigma),
-                                   out.data_ptr(), out64.data_ptr() if out64 is not None else None, ws.data_ptr(),
-                                   _lib.stream_of()), "unet_weight_map")
-    return (out, out64) if fp64 else out
+    d1 = d2 = None
+    if mode == "border":
+        need = lib.unet_weight_map_border_ws_bytes(n, h, w)
+        if need == 0:
+            raise ValueError(f"border weight maps need 1 <= h, w <= 16384, got {(n, h, w)}")
+        if return_distances:
+            d1 = torch.empty((n, h, w), dtype=torch.int32, device=labels.device)
+            d2 = torch.empty((n, h, w), dtype=torch.int32, device=labels.device)
+        ws = torch.empty(need, dtype=torch.uint8, device=labels.device)
+        _lib.check(lib.unet_weight_map_border(labels.data_ptr(), n, h, w, ctypes.c_double(w0), ctypes.c_double(sigma),
+                                              out.data_ptr(), _lib.ptr(out64), _lib.ptr(d1), _lib.ptr(d2),
+                                              ws.data_ptr(), _lib.stream_of()), "unet_weight_map_border")
+    else:
+        ws = torch.empty(lib.unet_weight_map_ws_bytes(n), dtype=torch.uint8, device=labels.device)
+        _lib.check(lib.unet_weight_map(labels.data_ptr(), n, h, w, ctypes.c_double(w0), ctypes.c_double(sigma),
+                                       out.data_ptr(), _lib.ptr(out64), ws.data_ptr(), _lib.stream_of()),
+                   "unet_weight_map")
+        if return_distances:
+            d1 = torch.zeros((n, h, w), dtype=torch.int32, device=labels.device)
+            d2 = torch.zeros((n, h, w), dtype=torch.int32, device=labels.device)
+    res = (out, out64) if fp64 else (out,)
+    if return_distances:
+        res = res + (d1, d2)
+    return res if len(res) > 1 else res[0]

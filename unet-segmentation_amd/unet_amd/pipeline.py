@@ -13,8 +13,12 @@ produces each minibatch with three device launches (ElasticDeform: two
 Gaussian passes + one warp, unet_amd.augment) and, for ``weights="warped"``,
 one weight-map launch on the warped labels; ``weights="static"`` (the
 reference's semantics) computes the maps of the unwarped labels once, on the
-device, and gathers them per batch.  Shuffling and rank sharding follow
-DataLoader(shuffle=True) / DistributedSampler (unet_amd.dist.ShardedIndices).
+device, and gathers them per batch.  ``weights="border"`` and
+``"border-warped"`` are the same two choices with the U-Net paper's
+border-aware maps (``weight_maps(mode="border")``: exact distances to the two
+nearest cells), the latter on the warped instance ids of each batch.
+Shuffling and rank sharding follow DataLoader(shuffle=True) /
+DistributedSampler (unet_amd.dist.ShardedIndices).
 
     data = HeLaBatches(images_u8, labels_u16, batch=4, out_hw=trainer.out_hw)
     for x, target, weight in data:              # target / weight: cropped views
@@ -27,6 +31,9 @@ import torch
 
 from .augment import ElasticDeform, weight_maps
 from .dist import ShardedIndices
+
+
+WEIGHT_MODES = ("static", "warped", "border", "border-warped")
 
 
 def center_crop_views(t, out_hw):
@@ -54,8 +61,9 @@ class HeLaBatches:
             raise ValueError("HeLaBatches keeps its frames on the HIP device (no CPU fallback)")
         if images.dtype != torch.uint8 or images.dim() != 3 or tuple(labels.shape) != tuple(images.shape):
             raise ValueError("images must be (N, H, W) uint8 and labels the same shape")
-        if weights not in ("static", "warped"):
-            raise ValueError("weights must be 'static' (the reference's precomputed maps) or 'warped'")
+        if weights not in WEIGHT_MODES:
+            raise ValueError("weights must be 'static' (the reference's precomputed maps), 'warped', 'border' "
+                             "(border-aware maps of the unwarped labels) or 'border-warped'")
         self.images = images.contiguous()
         if labels.dtype != torch.uint16:
             # instance ids are uint16 in the reference's man_seg*.tif files; a wider
@@ -71,7 +79,9 @@ class HeLaBatches:
         self.aug = ElasticDeform(alpha=alpha, sigma=sigma, noise=noise, generator=generator) if augment else None
         self.sampler = ShardedIndices(images.shape[0], world, rank, shuffle=shuffle, seed=seed)
         # preprocess_data.py: maps of the unwarped labels, computed once (device)
-        self.static_w = weight_maps(self.labels) if weights == "static" else None
+        # ("border": the same with the border-aware maps)
+        self.static_w = (weight_maps(self.labels, mode="border" if weights == "border" else "reference")
+                         if weights in ("static", "border") else None)
         self._lut = None
 
     def set_epoch(self, epoch):
@@ -87,7 +97,10 @@ class HeLaBatches:
         dev = self.images.device
         sel = torch.as_tensor(np.asarray(idx, dtype=np.int64), device=dev)
         img, lab = self.images.index_select(0, sel), self.labels.index_select(0, sel)
-        if self.augment:
+        ids = lab  # "border-warped" without augmentation: the batch's own ids
+        if self.augment and self.weights == "border-warped":
+            x, t8, ids = self.aug(img, lab, seeds=seeds, noise=noise, return_ids=True)
+        elif self.augment:
             x, t8 = self.aug(img, lab, seeds=seeds, noise=noise)
         else:  # ToTensor + mask > 0 on the undeformed labels (dataset.py:96-104; no uint8 cast without the warp)
             # ToTensor's exact uint8 / 255 (a host-built table: the device's
@@ -96,8 +109,10 @@ class HeLaBatches:
                 self._lut = (torch.arange(256, dtype=torch.float32) / 255.0).to(dev)
             x = self._lut[img.long()].unsqueeze(1)
             t8 = (lab.view(torch.int16) != 0).to(torch.uint8).unsqueeze(1)
-        if self.weights == "static":
+        if self.weights in ("static", "border"):
             w = self.static_w.index_select(0, sel)
+        elif self.weights == "border-warped":  # the paper's term on the warped instance ids
+            w = weight_maps(ids, mode="border")
         else:  # maps of the warped binary target (fixes the reference's unwarped maps)
             w = weight_maps(t8[:, 0].to(torch.int16).view(torch.uint16))
         target = center_crop_views(t8.to(torch.int64), self.out_hw)
