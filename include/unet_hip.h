@@ -389,7 +389,15 @@ int unet_linear_sum_assignment(long long nr, long long nc, const double* host_co
  *  "wgrad_early_u" 1 (default; env UNET_WGRAD_EARLY_U) = the Winograd weight
  *                  gradients' input transform is issued on the side stream
  *                  before the wait for the layer's dY; 0 = after it
- *                  (bit-identical results). */
+ *                  (bit-identical results).
+ *  "wgrad_plane"   1 (default; env UNET_WGRAD_PLANE) = the batched point GEMMs
+ *                  of the fp32 Winograd weight gradients run k_wgrad_plane
+ *                  (LDS-DMA ring) where their tile has one; 0 = k_wgrad
+ *                  (bit-identical results for the same tile and split).
+ *  "wgrad_oihw"    1 (default; env UNET_WGRAD_OIHW) = fp32 plans' Winograd
+ *                  weight gradients store torch's OIHW gradient from their
+ *                  output transform (see unet_wgrad_oihw_sites); 0 = packed
+ *                  store + permute (bit-identical results). */
 int unet_set_tuning(const char* key, int value);
 /* Text report of the tuned GEMM choices (one line per shape: key, heuristic
  * time, chosen variant and time).  Copies up to len-1 bytes + NUL into buf
@@ -412,6 +420,13 @@ long long unet_nondeterministic_sites(int reset);
  * Replaces nothing in the reference: it is a counter of this implementation's
  * schedule (models/unet_model.py:12,16 is the BatchNorm2d it differentiates). */
 long long unet_fused_bnb_sites(int reset);
+/* 3x3 layers of fp32 plans whose weight gradient ran a Winograd tile with its
+ * output transform storing torch's OIHW gradient directly
+ * (unet_set_tuning "wgrad_oihw"), so that the packed-gradient permute was
+ * skipped; reset != 0 also zeroes the count.  A counter of this
+ * implementation's schedule (models/unet_model.py:11,15 is the Conv2d whose
+ * weight it differentiates). */
+long long unet_wgrad_oihw_sites(int reset);
 /* Tuning database (cf. MIOpen's perf-db): unet_tuning_save writes every tuned
  * choice as "key<TAB>tile<TAB>split" lines (returns the count or -errno);
  * unet_tuning_load merges such a file, overriding equal keys (returns the

@@ -1504,7 +1504,10 @@ hipError_t launch_wgrad_v(const WgradArgs& a0, hipStream_t s, GemmChoice c) {
   }
   else if (splits == 1) a.slab = a.out;
   dim3 grid(a.Mo / t.bm, a.No / t.bn, splits * a.batch);
-  const hipError_t e = t.go_column(a, s, grid);
+  // batched GEMMs over contiguous planes (the Winograd point GEMMs): the same
+  // tile on the LDS-DMA ring, where it has a kernel (wgrad_plane.hip)
+  const hipError_t e = wgrad_plane_applies(a, t.bm, t.bn) ? launch_wgrad_plane(a, s, grid, t.bm, t.bn)
+                                                          : t.go_column(a, s, grid);
   if (e != hipSuccess || !a.slab || a.slab == a.out) return e;
   return launch_slab_reduce(a.slab, splits, a.batch, plane, a.batch_out, a.out, s);
 }

@@ -85,12 +85,29 @@ static void op_set_wino(IgemmArgs& a, void* ws, size_t ws_bytes, int ci, int co)
   a.wino_ws_bytes = op_wino_bytes(ci, co);
 }
 
+// Scratch of a forced Winograd weight gradient in unet_conv3x3_wgrad (tests:
+// wgrad_variant 71 / 74, 1071 / 1074; the built-in choice never takes one):
+// U, Vd and Mw of the larger of F(4x4) / F(6x6), then the point GEMMs' split
+// partials (slab forms: one split per 256 tiles at most, wgrad_splits).  Small
+// grids only -- 0 past 256 MB, where the forced tile then does not apply.
+static size_t op_wgrad_wino_bytes(int n, int h, int w, int ci, int co) {
+  return al256(wino_ws_bytes_grid(n, h, w, ci, co));
+}
+static size_t op_wgrad_slab_bytes(int n, int h, int w, int ci, int co) {
+  const long long t4 = (long long)n * ((h + 3) / 4) * ((w + 3) / 4);
+  return al256(sizeof(float) * 64 * (size_t)std::min<long long>(64, (t4 + 255) / 256) * ci * co);
+}
+static size_t op_wgrad_extra_bytes(int n, int h, int w, int ci, int co) {
+  const size_t b = op_wgrad_wino_bytes(n, h, w, ci, co) + op_wgrad_slab_bytes(n, h, w, ci, co);
+  return b <= ((size_t)256 << 20) ? b : 0;
+}
+
 size_t unet_conv_ws_bytes(int n, int h, int w, int ci, int co) {
   const size_t wb = al256(sizeof(float) * 9 * (size_t)ci * co);
   const size_t pad = al256(sizeof(float) * (size_t)n * (h + 2) * (w + 2) * co);  // (h-2+4)
   const size_t misc = al256(sizeof(float) * 4 * co) + al256(sizeof(double) * kStatGroups * 2 * co);
   const size_t x16 = al256(sizeof(uint16_t) * (size_t)n * h * w * ci);  // op_a16: bf16 copy of x
-  return 2 * wb + pad + misc + x16 + op_wino_bytes(ci, co);
+  return 2 * wb + pad + misc + x16 + op_wgrad_extra_bytes(n, h, w, ci, co) + op_wino_bytes(ci, co);
 }
 
 int unet_conv3x3_fwd(const float* x, int n, int h, int w, int ci, const float* wt, const float* bias, int co,
@@ -232,6 +249,14 @@ int unet_conv3x3_wgrad(const float* x, const float* dy, int n, int h, int w, int
     a.ga.s[0].h16 = a.ga.s[1].h16 = 1;
     a.gb.s[0].ptr = a.gb.s[1].ptr = reinterpret_cast<const float*>(x16);
     a.gb.s[0].h16 = a.gb.s[1].h16 = 1;
+  }
+  const WgradTile* forced = wgrad_tile(g_tune_wgrad >= 1000 ? g_tune_wgrad - 1000 : g_tune_wgrad);
+  if (forced && forced->family == WgradFamily::Wino && !a.bf16 && op_wgrad_extra_bytes(n, h, w, ci, co)) {
+    char* e = p + unet_conv_ws_bytes(n, h, w, ci, co) - op_wino_bytes(ci, co) - op_wgrad_extra_bytes(n, h, w, ci, co);
+    a.wino_ws = reinterpret_cast<float*>(e);
+    a.wino_ws_bytes = op_wgrad_wino_bytes(n, h, w, ci, co);
+    a.slab = reinterpret_cast<float*>(e + a.wino_ws_bytes);
+    a.slab_bytes = op_wgrad_slab_bytes(n, h, w, ci, co);
   }
   OPCK(launch_wgrad(a, s));
   OPCK(launch_permute_last2(dwp, co, 9, ci, dw, s));
@@ -548,6 +573,8 @@ int unet_set_tuning(const char* key, int value) {
   else if (k == "bnb_fuse") g_bnb_fuse = value;
   else if (k == "wgrad_early_u") g_wgrad_early_u = value;
   else if (k == "wgrad_fwd_u") g_wgrad_fwd_u = value;
+  else if (k == "wgrad_plane") g_wgrad_plane = value;
+  else if (k == "wgrad_oihw") g_wgrad_oihw = value;
   else if (k == "deterministic") g_deterministic = value != 0;  // 0: bf16 plans pool with the 4-channel kernel (A/B tests)
   else if (k == "op_precision") {
     if (value != UNET_PREC_FP32 && value != UNET_PREC_BF16 && value != UNET_PREC_BF16X3) return -EINVAL;

@@ -82,6 +82,12 @@ int g_wgrad_early_u = getenv("UNET_WGRAD_EARLY_U") ? atoi(getenv("UNET_WGRAD_EAR
 // during the FORWARD, on the side stream (idle there), into a per-layer buffer
 // the backward's point GEMMs read; read for the workspace layout at plan creation
 int g_wgrad_fwd_u = getenv("UNET_WGRAD_FWD_U") ? atoi(getenv("UNET_WGRAD_FWD_U")) : 0;
+// unet_set_tuning("wgrad_oihw", v) or UNET_WGRAD_OIHW (default on): a 3x3
+// layer whose weight gradient runs a Winograd tile has the output transform
+// store torch's OIHW gradient itself, and the plan skips that layer's
+// k_permute_slab (same values; 0 = packed store + permute, for the A/B test)
+int g_wgrad_oihw = getenv("UNET_WGRAD_OIHW") ? atoi(getenv("UNET_WGRAD_OIHW")) : 1;
+std::atomic<long long> g_wgrad_oihw_sites{0};
 }  // namespace unet
 
 namespace {
@@ -583,6 +589,7 @@ GemmChoice choose_wgrad(const Ctx& c, const WgradArgs& a) {
   if (capturing(c.s)) return GemmChoice{};
   WgradArgs t = a;
   t.out = c.f(c.p->tune_scratch);
+  t.out_oihw = nullptr;  // timed candidates write the scratch only
   // deterministic mode: the heuristic (atomics) is no candidate
   const float th = det ? -1.f : time_launch(c.s, [&] { return launch_wgrad(t, c.s); });
   GemmChoice best{};
@@ -641,10 +648,12 @@ void prep_wgrad(const Ctx& c, WgradArgs& a) {
   }
 }
 
-hipError_t run_wgrad(const Ctx& c, WgradArgs a) {
+// wrote_oihw (optional): set when the chosen tile stored a.out_oihw instead of a.out
+hipError_t run_wgrad(const Ctx& c, WgradArgs a, bool* wrote_oihw = nullptr) {
   prep_wgrad(c, a);
   const GemmChoice ch = choose_wgrad(c, a);
   if (unet::g_deterministic && !wgrad_choice_deterministic(ch)) ++unet::g_nondet_sites;
+  if (wrote_oihw) *wrote_oihw = a.out_oihw && wgrad_winograd_mt(a, ch) != 0;
   if (c.p->timing) c.p->xfl += wgrad_exec_flops(a, ch);
   return launch_wgrad_v(a, c.s, ch);
 }
@@ -1027,12 +1036,15 @@ int run_backward(unet_plan* p, void* const* prm, void* const* grd, const float* 
       CK(hipEventRecord(p->ev_dy[l], s));
       CK(hipStreamWaitEvent(sw, p->ev_dy[l], 0));
     }
+    bool oihw = false;
     {
       Timer t(p, sw, UNET_KC_CONV_WGRAD, conv_flops(L, n), 0, true, site_conv(l, 2));
       Timer tb(p, sw, UNET_KC_BOTTLENECK, conv_flops(L, n), 0, bottleneck_conv(l));
-      CK(run_wgrad(cw, w));
+      if (unet::g_wgrad_oihw && p->prec == UNET_PREC_FP32) w.out_oihw = P<float>(grd, L.gw);
+      CK(run_wgrad(cw, w, &oihw));
     }
-    CK(launch_permute_last2(c.f(L.dwp), L.co, 9, L.ci, P<float>(grd, L.gw), sw));
+    if (oihw) ++unet::g_wgrad_oihw_sites;  // a Winograd tile: its output transform stored OIHW
+    else CK(launch_permute_last2(c.f(L.dwp), L.co, 9, L.ci, P<float>(grd, L.gw), sw));
     // input gradient
     IgemmArgs a;
     a.a.s[0] = dy;
@@ -1587,6 +1599,9 @@ long long unet_nondeterministic_sites(int reset) {
 
 long long unet_fused_bnb_sites(int reset) {
   return reset ? unet::g_fused_bnb_sites.exchange(0) : unet::g_fused_bnb_sites.load();
+}
+long long unet_wgrad_oihw_sites(int reset) {
+  return reset ? unet::g_wgrad_oihw_sites.exchange(0) : unet::g_wgrad_oihw_sites.load();
 }
 long long unet_slab_fallbacks(int reset) {
   return reset ? g_slab_fallbacks.exchange(0) : g_slab_fallbacks.load();

@@ -118,6 +118,8 @@ extern std::atomic<long long> g_slab_fallbacks;
 extern int g_deterministic;
 extern int g_bnb_fuse;       // plan.hip: fp32 BN-backward apply fused with the F(6x6) dY transform
 extern int g_wgrad_early_u;  // plan.hip: Winograd weight gradients' U issued before the layer's dY
+extern int g_wgrad_plane;    // wgrad_plane.hip: batched fp32 point GEMMs on the LDS-DMA ring kernel
+extern int g_wgrad_oihw;     // plan.hip: Winograd weight gradients store torch's OIHW layout themselves
 extern std::atomic<long long> g_nondet_sites;
 
 struct WgradArgs {
@@ -131,6 +133,12 @@ struct WgradArgs {
   // slab modes (below) OVERWRITE it: the reduction assigns the sum of the
   // splits, a single split stores straight into it.
   float* out;
+  // optional (3x3 layers): torch's OIHW gradient [Mo][Cg][9].  A Winograd tile
+  // (71 / 74) then assigns its result there instead of the packed `out`
+  // (its output transform holds all nine taps of a (co, ci) pair), and the
+  // caller skips the permute; every other tile ignores it
+  // (wgrad_winograd_mt tells which ran)
+  float* out_oihw = nullptr;
   // optional split-partial slab (bf16 ring weight gradients, wgrad per_cu codes
   // >= 10): each pixel split stores its [Mo][No] partial with plain stores and
   // one reduction pass assigns their sum to out -- instead of per_cu x CUs x
@@ -343,6 +351,11 @@ hipError_t launch_slab_reduce(const float* slab, int splits, int batch, size_t p
 int wgrad_splits(const WgradArgs& a, const WgradTile& t, int per_cu, int& pps);
 // whether slab mode can hold `splits` partial planes (1 split: stores into out)
 bool wgrad_slab_fits(const WgradArgs& a, int splits);
+// k_wgrad_plane (wgrad_plane.hip): the bm x bn pixel-column tile's LDS-DMA ring
+// form for batched GEMMs over contiguous planes (the Winograd weight
+// gradients' point GEMMs), on launch_wgrad_v's grid; same bits as k_wgrad
+bool wgrad_plane_applies(const WgradArgs& a, int bm, int bn);
+hipError_t launch_wgrad_plane(const WgradArgs& a, hipStream_t s, dim3 grid, int bm, int bn);
 // out[i] = bf16(in[i]) (RNE), n a multiple of 4, in 16-B / out 8-B aligned;
 // lo (optional): lo[i] = bf16(in[i] - out[i]), the residual plane of split operands
 hipError_t launch_f2bf(const float* in, uint16_t* out, size_t n, hipStream_t s, uint16_t* lo = nullptr);

@@ -2157,31 +2157,66 @@ __global__ __launch_bounds__(256) void k_wino4_dy(Src dy, int Hg, int Wg, int Th
   }
 }
 
-// out[co][ky*3+kx][ci] = (G^T Mw[.][co][ci] G)[ky][kx]; the only writer of out
+// dW[ky*3+kx] = (G^T Mw[.][co][ci] G)[ky][kx] of the pair i = co * Ci + ci (all
+// nine taps) to the packed out[co][tap][ci], or (oihw, kernel-uniform) to
+// torch's out[co][ci][tap]: there a workgroup's 256 pairs are one contiguous
+// run of 2304 floats, which passes through LDS (9-float rows: conflict-free)
+// so the stores stay coalesced.  The only writer of out.
+__device__ __forceinline__ void wout_store(const float (&dwv)[9], long long i, long long n, int Ci,
+                                           float* __restrict__ out, int oihw) {
+  // the nine values opaque to the optimiser: nine adjacent LDS stores would
+  // seed a vectorised (packed-math) form of the transforms above with other
+  // mul / add contractions, i.e. other bits than the packed-layout kernel's
+  float dw[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    dw[t] = dwv[t];
+    asm volatile("" : "+v"(dw[t]));
+  }
+  if (!oihw) {
+    if (i >= n) return;
+    const int co = (int)(i / Ci), ci = (int)(i - (long long)co * Ci);
+#pragma unroll
+    for (int t = 0; t < 9; ++t) out[((size_t)co * 9 + t) * Ci + ci] = dw[t];
+    return;
+  }
+  __shared__ float st[256 * 9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) st[threadIdx.x * 9 + t] = dw[t];
+  __syncthreads();
+  const long long base = blockIdx.x * (long long)(256 * 9), lim = n * 9;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const int e = k * 256 + threadIdx.x;
+    if (base + e < lim) out[base + e] = st[e];
+  }
+}
+
 __global__ __launch_bounds__(256) void k_wino4_wout(const float* __restrict__ mw, int Co, int Ci,
-                                                    float* __restrict__ out) {
-  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (i >= (long long)Co * Ci) return;
-  const int co = (int)(i / Ci), ci = (int)(i - (long long)co * Ci);
+                                                    float* __restrict__ out, int oihw) {
+  const long long n = (long long)Co * Ci;
+  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x, il = i < n ? i : n - 1;
   const size_t plane = (size_t)Co * Ci;
   float w[3][6];
 #pragma unroll
   for (int bb = 0; bb < 6; ++bb) {
     float m[6];
 #pragma unroll
-    for (int a = 0; a < 6; ++a) m[a] = mw[(a * 6 + bb) * plane + i];
+    for (int a = 0; a < 6; ++a) m[a] = mw[(a * 6 + bb) * plane + il];
     float r[3];
     gt3(m, r);
 #pragma unroll
     for (int k = 0; k < 3; ++k) w[k][bb] = r[k];
   }
+  float dw[9];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     float r[3];
     gt3(w[k], r);
 #pragma unroll
-    for (int kx = 0; kx < 3; ++kx) out[((size_t)co * 9 + k * 3 + kx) * Ci + ci] = r[kx];
+    for (int kx = 0; kx < 3; ++kx) dw[k * 3 + kx] = r[kx];
   }
+  wout_store(dw, i, n, Ci, out, oihw);
 }
 
 // F(6x6) weight-gradient transforms (wgrad tile 74): Vd = A dY A^T with
@@ -2370,29 +2405,30 @@ hipError_t launch_bnb_wino6_dy(const float* dz, const float* y, const float* coe
 }
 
 __global__ __launch_bounds__(256) void k_wino6_wout(const float* __restrict__ mw, int Co, int Ci,
-                                                    float* __restrict__ out) {
-  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (i >= (long long)Co * Ci) return;
-  const int co = (int)(i / Ci), ci = (int)(i - (long long)co * Ci);
+                                                    float* __restrict__ out, int oihw) {
+  const long long n = (long long)Co * Ci;
+  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x, il = i < n ? i : n - 1;
   const size_t plane = (size_t)Co * Ci;
   float w[3][8];
 #pragma unroll
   for (int bb = 0; bb < 8; ++bb) {
     float m[8];
 #pragma unroll
-    for (int a = 0; a < 8; ++a) m[a] = mw[(a * 8 + bb) * plane + i];
+    for (int a = 0; a < 8; ++a) m[a] = mw[(a * 8 + bb) * plane + il];
     float r[3];
     gt8(m, r);
 #pragma unroll
     for (int k = 0; k < 3; ++k) w[k][bb] = r[k];
   }
+  float dw[9];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     float r[3];
     gt8(w[k], r);
 #pragma unroll
-    for (int kx = 0; kx < 3; ++kx) out[((size_t)co * 9 + k * 3 + kx) * Ci + ci] = r[kx];
+    for (int kx = 0; kx < 3; ++kx) dw[k * 3 + kx] = r[kx];
   }
+  wout_store(dw, i, n, Ci, out, oihw);
 }
 
 static long long wino_wgrad_tiles(const WgradArgs& a, int mt) {
@@ -2501,10 +2537,12 @@ hipError_t launch_wino_wgrad(const WgradArgs& a, hipStream_t s, WgradMode m, int
     if ((e = launch_wgrad_v(q, s, GemmChoice{tile, encode(pt, {per_cu, -1, use_slab})})) != hipSuccess) return e;
   }
   const long long no = (long long)Co * Ci;
+  const int oihw = a.out_oihw != nullptr;  // torch's layout straight from the transform: the caller skips its permute
+  float* const dw = oihw ? a.out_oihw : a.out;
   if (mt == 4)
-    hipLaunchKernelGGL(k_wino4_wout, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, s, Mw, Co, Ci, a.out);
+    hipLaunchKernelGGL(k_wino4_wout, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, s, Mw, Co, Ci, dw, oihw);
   else
-    hipLaunchKernelGGL(k_wino6_wout, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, s, Mw, Co, Ci, a.out);
+    hipLaunchKernelGGL(k_wino6_wout, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, s, Mw, Co, Ci, dw, oihw);
   return hipGetLastError();
 }
 
