@@ -397,7 +397,15 @@ int unet_linear_sum_assignment(long long nr, long long nc, const double* host_co
  *  "wgrad_oihw"    1 (default; env UNET_WGRAD_OIHW) = fp32 plans' Winograd
  *                  weight gradients store torch's OIHW gradient from their
  *                  output transform (see unet_wgrad_oihw_sites); 0 = packed
- *                  store + permute (bit-identical results). */
+ *                  store + permute (bit-identical results).
+ *  "igemm_plane"   1 (default; env UNET_IGEMM_PLANE) = the batched point GEMMs
+ *                  of the unfused fp32 Winograd forward / input-gradient tiles
+ *                  (70, 71) run k_igemm_plane (LDS-DMA ring) where their tile
+ *                  has one (1, 2, 3, 8, 9; see unet_igemm_plane_launches);
+ *                  0 = k_igemm (bit-identical results for the same tile).
+ *  "wino_point_tile" id (tests; default -1 = off): the unfused Winograd tiles
+ *                  run their point GEMMs on register-staged tile id (1-4, 6-9)
+ *                  where it fits, instead of the tuned or heuristic one. */
 int unet_set_tuning(const char* key, int value);
 /* Text report of the tuned GEMM choices (one line per shape: key, heuristic
  * time, chosen variant and time).  Copies up to len-1 bytes + NUL into buf
@@ -427,6 +435,12 @@ long long unet_fused_bnb_sites(int reset);
  * implementation's schedule (models/unet_model.py:11,15 is the Conv2d whose
  * weight it differentiates). */
 long long unet_wgrad_oihw_sites(int reset);
+/* Launches of k_igemm_plane, the LDS-DMA ring form of the batched point GEMMs
+ * of the unfused fp32 Winograd forward / input-gradient tiles
+ * (unet_set_tuning "igemm_plane"); reset != 0 also zeroes the count.  A counter
+ * of this implementation's schedule (models/unet_model.py:11,15 is the Conv2d
+ * those GEMMs compute). */
+long long unet_igemm_plane_launches(int reset);
 /* Tuning database (cf. MIOpen's perf-db): unet_tuning_save writes every tuned
  * choice as "key<TAB>tile<TAB>split" lines (returns the count or -errno);
  * unet_tuning_load merges such a file, overriding equal keys (returns the

@@ -1137,6 +1137,9 @@ static hipError_t go_igemm(const IgemmArgs& a, hipStream_t s) {
   if (a.batch > 1) {
     if (a.ksplit > 1 || a.batch_rows < 1) return hipErrorInvalidValue;
     dim3 grid((a.batch_rows + BM - 1) / BM, a.N / BN, a.batch);
+    // contiguous planes (the Winograd point GEMMs): the same tile on the
+    // LDS-DMA ring, where it has a kernel (igemm_plane.hip)
+    if (WM == 2 && WN == 2 && igemm_plane_applies(a, BM, BN, BK)) return launch_igemm_plane(a, s, grid, BM, BN, BK);
     hipLaunchKernelGGL((k_igemm<BM, BN, WM, WN, BK>), grid, dim3(WM * WN * 64), 0, s, a);
     return hipGetLastError();
   }

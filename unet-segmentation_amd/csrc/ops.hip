@@ -80,7 +80,22 @@ extern "C" {
 // per-op GEMMs (tests: unet_set_tuning("igemm_variant", t)); the built-in
 // choice of the per-op entry points never takes a Winograd tile
 static size_t op_wino_bytes(int ci, int co) { return al256(sizeof(float) * 36 * (size_t)ci * co); }
-static void op_set_wino(IgemmArgs& a, void* ws, size_t ws_bytes, int ci, int co) {
+static size_t op_wgrad_wino_bytes(int n, int h, int w, int ci, int co);
+static size_t op_wgrad_extra_bytes(int n, int h, int w, int ci, int co);
+// A forced unfused Winograd tile (70, 71: U, M and V in HBM) borrows the scratch
+// unet_conv_ws_bytes reserves for a forced Winograd weight gradient instead: it
+// holds the larger of F(2x2) / F(4x4) / F(6x6) over the n x h x w grid, which
+// covers the forward's (h - 2) x (w - 2) and the input gradient's h x w tiles
+// (the size is symmetric in Cg and N).
+static void op_set_wino(IgemmArgs& a, void* ws, int n, int h, int w, int ci, int co) {
+  const size_t ws_bytes = unet_conv_ws_bytes(n, h, w, ci, co);
+  const IgemmTile* forced = igemm_tile(g_tune_igemm);
+  if (forced && forced->family == IgemmFamily::Wino && op_wgrad_extra_bytes(n, h, w, ci, co)) {
+    a.wino_ws = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + ws_bytes - op_wino_bytes(ci, co) -
+                                         op_wgrad_extra_bytes(n, h, w, ci, co));
+    a.wino_ws_bytes = op_wgrad_wino_bytes(n, h, w, ci, co);
+    return;
+  }
   a.wino_ws = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + ws_bytes - op_wino_bytes(ci, co));
   a.wino_ws_bytes = op_wino_bytes(ci, co);
 }
@@ -145,7 +160,7 @@ int unet_conv3x3_fwd(const float* x, int n, int h, int w, int ci, const float* w
   a.K = 9 * ci;
   a.e.bias = bias;
   a.e.d[0] = Dst{y, h - 2, w - 2, co, 0, 0};
-  op_set_wino(a, ws, unet_conv_ws_bytes(n, h, w, ci, co), ci, co);
+  op_set_wino(a, ws, n, h, w, ci, co);
   OPCK(op_b_to_bf16(a, 9 * (size_t)ci * co, reinterpret_cast<char*>(ws) + al256(sizeof(float) * 9 * (size_t)ci * co),
                     s));
   OPCK(launch_igemm(a, s));
@@ -186,7 +201,7 @@ int unet_conv3x3_dgrad(const float* dy, int n, int h, int w, int ci, const float
   a.N = ci;
   a.K = 9 * co;
   a.e.d[0] = Dst{dx, h, w, ci, 0, 0};
-  op_set_wino(a, ws, unet_conv_ws_bytes(n, h, w, ci, co), ci, co);
+  op_set_wino(a, ws, n, h, w, ci, co);
   OPCK(op_b_to_bf16(a, 9 * (size_t)ci * co, wf, s));
   OPCK(launch_igemm(a, s));
   return 0;
@@ -575,6 +590,8 @@ int unet_set_tuning(const char* key, int value) {
   else if (k == "wgrad_fwd_u") g_wgrad_fwd_u = value;
   else if (k == "wgrad_plane") g_wgrad_plane = value;
   else if (k == "wgrad_oihw") g_wgrad_oihw = value;
+  else if (k == "igemm_plane") g_igemm_plane = value;
+  else if (k == "wino_point_tile") g_wino_point_tile = value;
   else if (k == "deterministic") g_deterministic = value != 0;  // 0: bf16 plans pool with the 4-channel kernel (A/B tests)
   else if (k == "op_precision") {
     if (value != UNET_PREC_FP32 && value != UNET_PREC_BF16 && value != UNET_PREC_BF16X3) return -EINVAL;

@@ -120,6 +120,9 @@ extern int g_bnb_fuse;       // plan.hip: fp32 BN-backward apply fused with the 
 extern int g_wgrad_early_u;  // plan.hip: Winograd weight gradients' U issued before the layer's dY
 extern int g_wgrad_plane;    // wgrad_plane.hip: batched fp32 point GEMMs on the LDS-DMA ring kernel
 extern int g_wgrad_oihw;     // plan.hip: Winograd weight gradients store torch's OIHW layout themselves
+extern int g_igemm_plane;    // igemm_plane.hip: batched fp32 forward / dgrad point GEMMs on the LDS-DMA ring kernel
+extern std::atomic<long long> g_igemm_plane_launches;  // k_igemm_plane launches (unet_igemm_plane_launches)
+extern int g_wino_point_tile;  // winograd.hip: forced tile of launch_wino's point GEMMs (tests), -1 = off
 extern std::atomic<long long> g_nondet_sites;
 
 struct WgradArgs {
@@ -356,6 +359,12 @@ bool wgrad_slab_fits(const WgradArgs& a, int splits);
 // gradients' point GEMMs), on launch_wgrad_v's grid; same bits as k_wgrad
 bool wgrad_plane_applies(const WgradArgs& a, int bm, int bn);
 hipError_t launch_wgrad_plane(const WgradArgs& a, hipStream_t s, dim3 grid, int bm, int bn);
+// k_igemm_plane (igemm_plane.hip): the bm x bn x bk register-staged tile's
+// LDS-DMA ring form for batched GEMMs over contiguous planes (the Winograd
+// forward / input-gradient point GEMMs), on go_igemm's batched grid; same bits
+// as k_igemm
+bool igemm_plane_applies(const IgemmArgs& a, int bm, int bn, int bk);
+hipError_t launch_igemm_plane(const IgemmArgs& a, hipStream_t s, dim3 grid, int bm, int bn, int bk);
 // out[i] = bf16(in[i]) (RNE), n a multiple of 4, in 16-B / out 8-B aligned;
 // lo (optional): lo[i] = bf16(in[i] - out[i]), the residual plane of split operands
 hipError_t launch_f2bf(const float* in, uint16_t* out, size_t n, hipStream_t s, uint16_t* lo = nullptr);

@@ -741,6 +741,16 @@ bool wino_applies(const IgemmArgs& a, int mt) {
   return a.wino_ws != nullptr && wino_bytes((mt + 2) * (mt + 2), T, g.Cg, a.N) <= a.wino_ws_bytes;
 }
 
+// unet_set_tuning("wino_point_tile", id): launch_wino runs its point GEMMs on
+// tile id where it fits, whatever the caller chose (-1 = off).  Only the
+// register-staged tiles take the batched launch form (the tuner's inner list).
+int g_wino_point_tile = -1;
+static bool wino_point_tile_ok(int id) {
+  for (int t : {1, 2, 3, 4, 6, 7, 8, 9})
+    if (t == id) return true;
+  return false;
+}
+
 hipError_t launch_wino(const IgemmArgs& a, hipStream_t s, int mt) {
   if (!wino_applies(a, mt)) return hipErrorInvalidValue;
   const Gather& g = a.a;
@@ -792,6 +802,8 @@ hipError_t launch_wino(const IgemmArgs& a, hipStream_t s, int mt) {
     // 256 x 128 tiles when they give two rounds of workgroups, else 128 x 128
     // (register-staged k_igemm: the batched launch form)
     int tile = a.wino_choice.tile;  // autotuned (GemmChoice split 100 + tile), else the heuristic
+    // unet_set_tuning("wino_point_tile", id) (tests): a register-staged tile the heuristic never picks
+    if (wino_point_tile_ok(g_wino_point_tile) && igemm_tile_fits(q, g_wino_point_tile)) tile = g_wino_point_tile;
     if (tile <= 0 || !igemm_tile_fits(q, tile)) {
       const long long t256 = ((T + 255) / 256) * (a.N / 128) * P;
       tile = (a.N % 128 == 0 && t256 >= 2 * num_cus()) ? 4 : (a.N % 128 == 0 ? 1 : 8);

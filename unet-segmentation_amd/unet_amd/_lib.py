@@ -101,6 +101,7 @@ SIGNATURES = {
     "unet_nondeterministic_sites": (ctypes.c_longlong, [_i]),
     "unet_fused_bnb_sites": (ctypes.c_longlong, [_i]),
     "unet_wgrad_oihw_sites": (ctypes.c_longlong, [_i]),
+    "unet_igemm_plane_launches": (ctypes.c_longlong, [_i]),
     "unet_tuning_save": (_i, [ctypes.c_char_p]),
     "unet_tuning_load": (_i, [ctypes.c_char_p]),
 }
@@ -161,7 +162,7 @@ def stream_of(device=None):
 _HASHED = ["igemm.hip", "igemm_bf16.hip", "conv3_dma.hip", "conv3_ring.hip", "winograd.hip", "elementwise.hip", "elastic.hip",
            "tiling.hip", "weightmap.hip", "postproc.hip", "track.hip", "ops.hip", "plan.hip", "wgrad3_ring.hip",
            "conv3_ring_pt.hip", "peak.hip", "gemm_ring.hip", "wgradT_ring.hip", "conv3_flat.hip", "conv3_c64.hip", "gemm_ring_p1.hip",
-           "gemm_ring_p2.hip", "wgrad_plane.hip", "unet_internal.h", "gemm_common.h", "ring_common.h", "conv3_ring_kernel.h",
+           "gemm_ring_p2.hip", "wgrad_plane.hip", "igemm_plane.hip", "unet_internal.h", "gemm_common.h", "ring_common.h", "conv3_ring_kernel.h",
            os.path.join("..", "..", "include", "unet_hip.h")]
 
 
