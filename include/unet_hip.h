@@ -327,6 +327,95 @@ int unet_tracker_tracks(const unet_tracker* t, int32_t* host_out, int cap);
 int unet_linear_sum_assignment(long long nr, long long nc, const double* host_cost, int64_t* host_row_ind,
                                int64_t* host_col_ind);
 
+/* Cell Tracking Challenge measures (the reference's README step 8 and its
+ * EvaluationSoftware/{Win,Mac}/{SEG,DET,TRA}Measure binaries, whose Linux
+ * builds are absent): SEG, DET and TRA of a 2-D result sequence against its
+ * ground truth.  The GPU builds the sparse overlap records of whole stacks of
+ * frame pairs, chunk by chunk: 2 + 2 R kernel launches and 1 + R stream
+ * synchronisations per chunk of frames, where R, the rounds the chunk's tables
+ * take through the workspace, is 1 unless the frames need more than
+ * unet_ctc_ws_bytes provides for (below); a round that yields more than
+ * 65,536 overlap records takes one more synchronisation.  The host side, plain
+ * C++, matches objects, builds the two acyclic oriented graphs and counts the
+ * operations.
+ *   Matching: in a frame, result object S matches reference object R iff
+ *     2 |R and S| > |R| (integers, strict).
+ *   SEG: mean over the reference objects of the SEG frames of
+ *     |R and S| / |R or S| for the matching S, 0 without one.
+ *   Graphs (TRA frames): a vertex is a (frame, label) pair present in the
+ *     image.  Per track row "L B E P", in the table's order: if P != 0 the
+ *     parent link from P's last present vertex to L's first, then the track
+ *     links between L's consecutive present vertices within [B, E].
+ *   Operations: NS = m - 1 for a RES vertex matched by m > 1 GT vertices, FN =
+ *     unmatched GT vertex, FP = unmatched RES vertex; with "unique" = matched
+ *     by exactly one GT vertex: ED = RES edge with both ends unique and no GT
+ *     edge between their GT vertices, EC = such an edge whose GT edge has the
+ *     other kind, EA = GT edge without (both ends matched, both RES vertices
+ *     unique, RES edge between them).
+ *   AOGM = 5 NS + 10 FN + FP + ED + 1.5 EA + EC; AOGM0 = 10 |V_GT| + 1.5 |E_GT|;
+ *   TRA = 1 - min(AOGM, AOGM0) / AOGM0; DET the same from the vertex terms and
+ *     10 |V_GT| alone.
+ *   unet_ctc_add_frames: t frame pairs gt[i], res[i] of (h, w) uint16 labels
+ *     (any value 0..65535, 0 = background) on the device, frame numbers on the
+ *     host; kind UNET_CTC_SEG or UNET_CTC_TRA; ws >= unet_ctc_ws_bytes(t, h, w)
+ *     bytes, 256-byte aligned; h w < 2^31.  Synchronises the stream.  t = 0
+ *     only records (and checks) the frame size.  All or none: where the call
+ *     fails, also in a later chunk, the evaluator holds none of its frames.  -EINVAL where h, w differ
+ *     from an earlier call's ("the stacks' sizes differ").
+ *   unet_ctc_ws_bytes(t, h, w), with c = min(t, 1024), k = min(t,
+ *     "ctc_chunk_frames" as set at the time of the call) and P = h w:
+ *     c x (4 B + 2 x 8 KB bitmaps + 2 x 8 KB prefix + 8 B counts + 32 B
+ *     descriptor) + a table region of max(8 B x pow2ceil(2 P), k x 256 KB) +
+ *     16 B x (1 + max(P, 4096, k x 16384)) records, each part rounded up to
+ *     256 B.  A frame is charged n = min((n_gt + 1)(n_res + 1), its runs of
+ *     equal non-background (gt, res) keys along 16-pixel pieces, P) records,
+ *     and a table of 4 B x (n_gt + 1)(n_res + 1) (dense) or 8 B x pow2ceil(2 n)
+ *     (hashed).  A chunk passes in one round while the charges of its frames
+ *     fit both regions -- always for frames of up to 16,384 such runs, the
+ *     size the regions allow per chunk frame; any single frame fits alone, so
+ *     at worst a round holds one frame.
+ *   unet_ctc_add_frame_host: the same frame from host tables, no device work:
+ *     ascending labels (1..65535) and areas of both sides and n_pairs rows
+ *     (gt label, res label, |and|) of int64.  n_res < 0 states that the GT
+ *     frame has no RES frame: -ENODATA.
+ *   unet_ctc_set_tracks: rows (label, begin, end, parent) of man_track.txt
+ *     (UNET_CTC_GT) or res_track.txt (UNET_CTC_RES), host, in file order.
+ *   unet_ctc_measures: out[3] = SEG, DET, TRA (NaN where nothing was added for
+ *     a measure, TRA also while a side has no track table); counts[8] = NS, FN,
+ *     FP, ED, EA, EC, |V_GT|, |E_GT| (may be NULL).  -ENOENT: a label occurs
+ *     in an image but has no track row; -ESRCH: a parent id has no row;
+ *     unet_last_error() names the side, frame and label.
+ *   unet_ctc_log: the text of the evaluator's TRA_log.txt (six sections, the
+ *     rule, "TRA measure: %.6f"); copies up to cap - 1 bytes + NUL, returns
+ *     the full size including the NUL, or -errno as unet_ctc_measures.
+ *   unet_ctc_num_frames / _frame_sizes (out[4] = frame number, n_gt, n_res,
+ *     n_pairs) / _frame_tables: read a stored frame back (frames are ordered
+ *     by frame number once measures or the log were asked for, by insertion
+ *     before); any output pointer may be NULL.
+ *   unet_ctc_stats: out[6] = chunks, kernel launches (2 per chunk + 2 per
+ *     round), stream synchronisations, frames counted densely, frames counted
+ *     by hash, overlap records read.
+ * Tuning: "ctc_chunk_frames" and "ctc_dense_cells" of unet_set_tuning. */
+enum { UNET_CTC_SEG = 0, UNET_CTC_TRA = 1 };
+enum { UNET_CTC_GT = 0, UNET_CTC_RES = 1 };
+typedef struct unet_ctc unet_ctc;
+unet_ctc* unet_ctc_create(void);
+void unet_ctc_destroy(unet_ctc* c);
+size_t unet_ctc_ws_bytes(int t, int h, int w);
+int unet_ctc_add_frames(unet_ctc* c, int kind, const uint16_t* gt, const uint16_t* res, const int32_t* host_frames,
+                        int t, int h, int w, void* ws, unet_stream_t stream);
+int unet_ctc_add_frame_host(unet_ctc* c, int kind, int frame, int n_gt, const int32_t* host_gt_labels,
+                            const int64_t* host_gt_areas, int n_res, const int32_t* host_res_labels,
+                            const int64_t* host_res_areas, int n_pairs, const int64_t* host_pairs);
+int unet_ctc_set_tracks(unet_ctc* c, int side, const int32_t* host_rows, int n);
+int unet_ctc_measures(unet_ctc* c, double* host_out, int64_t* host_counts);
+long long unet_ctc_log(unet_ctc* c, char* buf, size_t cap);
+int unet_ctc_num_frames(const unet_ctc* c, int kind);
+int unet_ctc_frame_sizes(const unet_ctc* c, int kind, int index, int32_t* host_out);
+int unet_ctc_frame_tables(const unet_ctc* c, int kind, int index, int32_t* host_gt_labels, int64_t* host_gt_areas,
+                          int32_t* host_res_labels, int64_t* host_res_areas, int64_t* host_pairs);
+int unet_ctc_stats(const unet_ctc* c, int64_t* host_out);
+
 /* Tuning hooks, process-global:
  *  "autotune"      1 (default, or env UNET_AUTOTUNE) = the plan times the
  *                  applicable GEMM variants (tile shape, split-K, wgrad pixel
@@ -405,7 +494,12 @@ int unet_linear_sum_assignment(long long nr, long long nc, const double* host_co
  *                  0 = k_igemm (bit-identical results for the same tile).
  *  "wino_point_tile" id (tests; default -1 = off): the unfused Winograd tiles
  *                  run their point GEMMs on register-staged tile id (1-4, 6-9)
- *                  where it fits, instead of the tuned or heuristic one. */
+ *                  where it fits, instead of the tuned or heuristic one.
+ *  "ctc_chunk_frames" frames per chunk of unet_ctc_add_frames (1..1024; -1 =
+ *                  the default, 32); unet_ctc_ws_bytes reads it.
+ *  "ctc_dense_cells" largest (n_gt + 1)(n_res + 1) that unet_ctc_add_frames
+ *                  counts in a dense LDS table (0..8192, 0 = every frame by
+ *                  hash; -1 = the default, 4096). */
 int unet_set_tuning(const char* key, int value);
 /* Text report of the tuned GEMM choices (one line per shape: key, heuristic
  * time, chosen variant and time).  Copies up to len-1 bytes + NUL into buf

@@ -5,9 +5,11 @@
 // segment table, argument validation of the C ABI, the linear sum assignment
 // (random, tied, rectangular, degenerate matrices; checked for a valid
 // assignment and against brute force on small ones), the tracker's host step
-// on a synthetic sequence, the tuning report, and the GEMM variant selection
+// on a synthetic sequence, the Cell Tracking Challenge evaluator's host entry
+// points (measures, log, error paths), the tuning report, and the GEMM variant selection
 // (tile tables, fits, candidate lists, forced knobs) over synthetic launch
 // arguments, compared line for line with tests/golden/gemm_selection.txt.
+#include <cerrno>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -149,6 +151,95 @@ static void test_tracker() {
   unet_tracker_destroy(t);
   CHECK(unet_tracker_create(0, 8, 0.3, 0.1, 2) == nullptr);
   unet_tracker_destroy(nullptr);
+}
+
+static void test_ctc() {
+  // two frames, GT objects 1 and 2 in both
+  const int32_t gl[] = {1, 2};
+  const int64_t ga[] = {10, 20};
+  const int32_t gt_rows[] = {1, 0, 1, 0, 2, 0, 1, 0};
+  {  // RES = GT: 1 / 1 / 1, no operation
+    unet_ctc* c = unet_ctc_create();
+    CHECK(c != nullptr);
+    const int64_t pairs[] = {1, 1, 10, 2, 2, 20};
+    for (int f = 0; f < 2; ++f) CHECK(unet_ctc_add_frame_host(c, UNET_CTC_TRA, f, 2, gl, ga, 2, gl, ga, 2, pairs) == 0);
+    CHECK(unet_ctc_add_frame_host(c, UNET_CTC_SEG, 1, 2, gl, ga, 2, gl, ga, 2, pairs) == 0);
+    CHECK(unet_ctc_add_frame_host(c, UNET_CTC_SEG, 1, 2, gl, ga, 2, gl, ga, 2, pairs) == -EEXIST);
+    double out[3];
+    int64_t n[8];
+    CHECK(unet_ctc_measures(c, out, n) == 0 && out[0] == 1.0 && out[1] == 1.0 && std::isnan(out[2]));  // no tracks yet
+    CHECK(unet_ctc_set_tracks(c, UNET_CTC_GT, gt_rows, 2) == 0 && unet_ctc_set_tracks(c, UNET_CTC_RES, gt_rows, 2) == 0);
+    CHECK(unet_ctc_measures(c, out, n) == 0 && out[0] == 1.0 && out[1] == 1.0 && out[2] == 1.0);
+    CHECK(n[0] + n[1] + n[2] + n[3] + n[4] + n[5] == 0 && n[6] == 4 && n[7] == 2);
+    const long long need = unet_ctc_log(c, nullptr, 0);
+    CHECK(need > 0);
+    std::vector<char> buf((size_t)need), cut(8);
+    CHECK(unet_ctc_log(c, buf.data(), buf.size()) == need && std::strlen(buf.data()) + 1 == (size_t)need);
+    CHECK(std::strstr(buf.data(), "TRA measure: 1.000000\n") != nullptr);
+    CHECK(unet_ctc_log(c, cut.data(), cut.size()) == need && std::strlen(cut.data()) == 7);
+    int32_t sz[4];
+    CHECK(unet_ctc_num_frames(c, UNET_CTC_TRA) == 2 && unet_ctc_frame_sizes(c, UNET_CTC_TRA, 1, sz) == 0);
+    CHECK(sz[0] == 1 && sz[1] == 2 && sz[2] == 2 && sz[3] == 2);
+    int64_t pr[6];
+    CHECK(unet_ctc_frame_tables(c, UNET_CTC_TRA, 1, nullptr, nullptr, nullptr, nullptr, pr) == 0 && pr[5] == 20);
+    CHECK(unet_ctc_frame_sizes(c, UNET_CTC_TRA, 2, sz) != 0);
+    unet_ctc_destroy(c);
+  }
+  {  // a RES vertex over both GT objects, a half-covered object, an extra one
+    unet_ctc* c = unet_ctc_create();
+    const int32_t r0[] = {1}, r1[] = {1, 3};
+    const int64_t a0[] = {30}, a1[] = {10, 20};
+    const int64_t p0[] = {1, 1, 10, 2, 1, 20}, p1[] = {1, 1, 10, 2, 3, 10};  // 2 * 10 > 20 is false
+    CHECK(unet_ctc_add_frame_host(c, UNET_CTC_TRA, 1, 2, gl, ga, 2, r1, a1, 2, p1) == 0);
+    CHECK(unet_ctc_add_frame_host(c, UNET_CTC_TRA, 0, 2, gl, ga, 1, r0, a0, 2, p0) == 0);
+    const int32_t res_rows[] = {1, 0, 1, 0, 3, 1, 1, 0};
+    CHECK(unet_ctc_set_tracks(c, UNET_CTC_GT, gt_rows, 2) == 0 && unet_ctc_set_tracks(c, UNET_CTC_RES, res_rows, 2) == 0);
+    double out[3];
+    int64_t n[8];
+    CHECK(unet_ctc_measures(c, out, n) == 0);
+    CHECK(n[0] == 1 && n[1] == 1 && n[2] == 1 && n[3] == 0 && n[4] == 2 && n[5] == 0 && n[6] == 4 && n[7] == 2);
+    CHECK(std::isnan(out[0]) && out[1] == 1.0 - 16.0 / 40.0 && out[2] == 1.0 - 19.0 / 43.0);
+    // a label without a row, then a parent without one
+    const int32_t short_rows[] = {1, 0, 1, 0}, orphan[] = {1, 0, 1, 0, 3, 1, 1, 7};
+    CHECK(unet_ctc_set_tracks(c, UNET_CTC_RES, short_rows, 1) == 0);
+    CHECK(unet_ctc_measures(c, out, n) == -ENOENT && std::strstr(unet_last_error(), "RES label 3") != nullptr &&
+          std::strstr(unet_last_error(), "frame 1") != nullptr);
+    CHECK(unet_ctc_log(c, nullptr, 0) == -ENOENT);
+    CHECK(unet_ctc_set_tracks(c, UNET_CTC_RES, orphan, 2) == 0);
+    CHECK(unet_ctc_measures(c, out, n) == -ESRCH && std::strstr(unet_last_error(), "parent 7") != nullptr);
+    CHECK(unet_ctc_set_tracks(c, UNET_CTC_RES, res_rows, 2) == 0 && unet_ctc_measures(c, out, n) == 0);
+    // argument errors
+    const int32_t twice[] = {1, 0, 1, 0, 1, 0, 1, 0}, unsorted[] = {2, 1};
+    CHECK(unet_ctc_set_tracks(c, UNET_CTC_RES, twice, 2) == -EINVAL);
+    CHECK(unet_ctc_set_tracks(c, 2, twice, 1) == -EINVAL);
+    CHECK(unet_ctc_add_frame_host(c, UNET_CTC_SEG, 5, 2, gl, ga, -1, nullptr, nullptr, 0, nullptr) == -ENODATA);
+    CHECK(std::strstr(unet_last_error(), "frame 5") != nullptr);
+    CHECK(unet_ctc_add_frame_host(c, UNET_CTC_SEG, 5, 2, unsorted, ga, 0, nullptr, nullptr, 0, nullptr) == -EINVAL);
+    const int64_t big[] = {1, 1, 11}, missing[] = {1, 2, 1};
+    CHECK(unet_ctc_add_frame_host(c, UNET_CTC_SEG, 5, 2, gl, ga, 1, r0, a0, 1, big) == -EINVAL);
+    CHECK(unet_ctc_add_frame_host(c, UNET_CTC_SEG, 5, 2, gl, ga, 1, r0, a0, 1, missing) == -EINVAL);
+    CHECK(unet_ctc_add_frame_host(c, 7, 5, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr) == -EINVAL);
+    // frame sizes (t = 0 does no device work)
+    CHECK(unet_ctc_add_frames(c, UNET_CTC_TRA, nullptr, nullptr, nullptr, 0, 37, 53, nullptr, nullptr) == 0);
+    CHECK(unet_ctc_add_frames(c, UNET_CTC_TRA, nullptr, nullptr, nullptr, 0, 37, 54, nullptr, nullptr) == -EINVAL);
+    CHECK(std::strstr(unet_last_error(), "sizes differ") != nullptr);
+    CHECK(unet_ctc_add_frames(c, UNET_CTC_TRA, nullptr, nullptr, nullptr, 1, 37, 53, nullptr, nullptr) == -EINVAL);
+    unet_ctc_destroy(c);
+  }
+  // workspace formula: grows with the pixels of one frame and the chunk, not with 65536^2
+  CHECK(unet_ctc_ws_bytes(0, 8, 8) == 0 && unet_ctc_ws_bytes(1, 65536, 65536) == 0);
+  const size_t w1 = unet_ctc_ws_bytes(1, 512, 512), w84 = unet_ctc_ws_bytes(84, 512, 512);
+  CHECK(w1 > 0 && w1 % 256 == 0 && w84 > w1 && w84 < (64u << 20));
+  CHECK(unet_ctc_ws_bytes(5000, 512, 512) == unet_ctc_ws_bytes(1024, 512, 512));
+  // the table and record regions grow with the frames per chunk
+  CHECK(unet_set_tuning("ctc_chunk_frames", 8) == 0 && unet_ctc_ws_bytes(84, 64, 64) < w84);
+  const size_t s8 = unet_ctc_ws_bytes(84, 64, 64);
+  CHECK(unet_set_tuning("ctc_chunk_frames", 64) == 0 && unet_ctc_ws_bytes(84, 64, 64) > s8);
+  CHECK(unet_set_tuning("ctc_chunk_frames", 0) != 0 && unet_set_tuning("ctc_chunk_frames", -2) != 0);
+  CHECK(unet_set_tuning("ctc_dense_cells", -2) != 0 && unet_set_tuning("ctc_dense_cells", 0) == 0);
+  CHECK(unet_set_tuning("ctc_chunk_frames", -1) == 0 && unet_set_tuning("ctc_dense_cells", -1) == 0);  // defaults
+  CHECK(unet_ctc_ws_bytes(84, 512, 512) == w84);
+  unet_ctc_destroy(nullptr);
 }
 
 static void test_misc() {
@@ -419,6 +510,7 @@ int main(int argc, char** argv) {
   test_plans();
   test_lsap();
   test_tracker();
+  test_ctc();
   test_misc();
   if (argc > 1) test_selection(argv[1], argc > 2 && std::strcmp(argv[2], "--record") == 0);
   else CHECK(!"usage: host_selftest tests/golden/gemm_selection.txt [--record]");

@@ -14,7 +14,7 @@ using namespace unet;
 namespace unet {
 extern int g_tune_igemm, g_tune_wgrad, g_autotune, g_force_split, g_force_tile, g_concurrent, g_wino_max,
     g_wino_dgrad_max, g_wino_wgrad_max, g_bf16_norm, g_bn_fold, g_wino4_fwd_min_cg, g_wino4_fwd_small_cg,
-    g_maxpool_vec8, g_wgrad_fwd_u;
+    g_maxpool_vec8, g_wgrad_fwd_u, g_ctc_chunk_frames, g_ctc_dense_cells;
 hipError_t launch_fill(float* p, size_t n, float v, hipStream_t s);
 hipError_t launch_pair_sum(const double* st, int g, int c, float* out, hipStream_t s);
 }  // namespace unet
@@ -592,6 +592,10 @@ int unet_set_tuning(const char* key, int value) {
   else if (k == "wgrad_oihw") g_wgrad_oihw = value;
   else if (k == "igemm_plane") g_igemm_plane = value;
   else if (k == "wino_point_tile") g_wino_point_tile = value;
+  else if (k == "ctc_chunk_frames" || k == "ctc_dense_cells") {  // ctc.hip clamps them to what it supports
+    if (value < -1 || (value == 0 && k == "ctc_chunk_frames")) return -EINVAL;  // -1 = the default
+    (k == "ctc_chunk_frames" ? g_ctc_chunk_frames : g_ctc_dense_cells) = value;
+  }
   else if (k == "deterministic") g_deterministic = value != 0;  // 0: bf16 plans pool with the 4-channel kernel (A/B tests)
   else if (k == "op_precision") {
     if (value != UNET_PREC_FP32 && value != UNET_PREC_BF16 && value != UNET_PREC_BF16X3) return -EINVAL;

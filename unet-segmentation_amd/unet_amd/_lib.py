@@ -94,6 +94,18 @@ SIGNATURES = {
     "unet_tracker_num_tracks": (_i, [_vp]),
     "unet_tracker_tracks": (_i, [_vp, _vp, _i]),
     "unet_linear_sum_assignment": (_i, [ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp]),
+    "unet_ctc_create": (_vp, []),
+    "unet_ctc_destroy": (None, [_vp]),
+    "unet_ctc_ws_bytes": (_sz, [_i, _i, _i]),
+    "unet_ctc_add_frames": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "unet_ctc_add_frame_host": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "unet_ctc_set_tracks": (_i, [_vp, _i, _vp, _i]),
+    "unet_ctc_measures": (_i, [_vp, _vp, _vp]),
+    "unet_ctc_log": (ctypes.c_longlong, [_vp, ctypes.c_char_p, _sz]),
+    "unet_ctc_num_frames": (_i, [_vp, _i]),
+    "unet_ctc_frame_sizes": (_i, [_vp, _i, _i, _vp]),
+    "unet_ctc_frame_tables": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "unet_ctc_stats": (_i, [_vp, _vp]),
     "unet_set_tuning": (_i, [ctypes.c_char_p, _i]),
     "unet_tuning_report": (_sz, [ctypes.c_char_p, _sz]),
     "unet_tuning_reset": (_i, []),
@@ -162,7 +174,7 @@ def stream_of(device=None):
 _HASHED = ["igemm.hip", "igemm_bf16.hip", "conv3_dma.hip", "conv3_ring.hip", "winograd.hip", "elementwise.hip", "elastic.hip",
            "tiling.hip", "weightmap.hip", "postproc.hip", "track.hip", "ops.hip", "plan.hip", "wgrad3_ring.hip",
            "conv3_ring_pt.hip", "peak.hip", "gemm_ring.hip", "wgradT_ring.hip", "conv3_flat.hip", "conv3_c64.hip", "gemm_ring_p1.hip",
-           "gemm_ring_p2.hip", "wgrad_plane.hip", "igemm_plane.hip", "unet_internal.h", "gemm_common.h", "ring_common.h", "conv3_ring_kernel.h",
+           "gemm_ring_p2.hip", "wgrad_plane.hip", "igemm_plane.hip", "ctc.hip", "unet_internal.h", "gemm_common.h", "ring_common.h", "conv3_ring_kernel.h",
            os.path.join("..", "..", "include", "unet_hip.h")]
 
 
