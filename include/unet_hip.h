@@ -416,6 +416,46 @@ int unet_ctc_frame_tables(const unet_ctc* c, int kind, int index, int32_t* host_
                           int32_t* host_res_labels, int64_t* host_res_areas, int64_t* host_pairs);
 int unet_ctc_stats(const unet_ctc* c, int64_t* host_out);
 
+/* Warping error and pixel error (Jain et al., "Boundary learning by
+ * optimization with topological constraints", CVPR 2010; the measures the
+ * U-Net paper ranks by; utils/metrics.py ends in a calculate_warping_error
+ * placeholder).  gt (n, h, w) uint16 instance ids, pred (n, h, w) uint8 with
+ * > 0 = foreground (T); all on the device.
+ *   G0: separate == 0: gt > 0; else gt > 0 and no in-frame pixel of the 3x3
+ *     neighbourhood carries another non-zero id (a background ridge between
+ *     touching cells).
+ *   Foreground is 8-connected, background 4-connected; outside the frame is
+ *     background and never flips.  A pixel is simple iff the foreground of its
+ *     8-neighbourhood N* is one 8-connected component and exactly one
+ *     4-connected background component of N* is 4-adjacent to it: a function
+ *     of the 8 neighbour bits (bit k = neighbour k of N, NE, E, SE, S, SW, W,
+ *     NW), which unet_simple_point_table writes as out[256] of 0 / 1 (116
+ *     ones; host only, built from the definition).
+ *   Mask M: the pixels whose (2 radius + 1)^2 window, clipped to the frame,
+ *     holds both a foreground and a background pixel of G0; radius -1 = the
+ *     whole frame, 0 = empty.
+ *   Schedule: L = G0; one sweep is four sub-steps s = 0..3, each flipping at
+ *     once every pixel with y & 1 == s >> 1, x & 1 == s & 1, in M, L != T and
+ *     simple in L as it stands when the sub-step starts.  The loop ends after
+ *     a sweep without a flip, or after max_sweeps sweeps (0 = no limit).
+ *   counts (device, n x 5 int64): pixel error |G0 != T|, warping error
+ *     |L != T| over the frame, flips, sweeps run (the last, empty one
+ *     included), converged (1 iff the last sweep flipped nothing).  pixel
+ *     error - warping error == flips.
+ *   warped (may be NULL): (n, h, w) uint8, the final L as 0 / 1.
+ * One workgroup per frame, one launch, no host synchronisation.  The frame's
+ * four bit planes live in LDS where they fit (4 (h + 2)(ceil(w / 32) + 2)
+ * words within 160 KB: 512 x 512 does), else -- or with UNET_WARP_FORCE_WS in
+ * flags -- in ws (>= unet_warping_error_ws_bytes, 256-byte aligned; may be
+ * NULL where the planes fit LDS and the flag is clear).
+ * -EINVAL before any launch (and a workspace size of 0) for n, h or w < 1,
+ * radius < -1 or > 255, max_sweeps < 0, n h w >= 2^31. */
+enum { UNET_WARP_FORCE_WS = 1 };
+size_t unet_warping_error_ws_bytes(int n, int h, int w);
+int unet_warping_error(const uint16_t* gt, const uint8_t* pred, int n, int h, int w, int radius, int separate,
+                       int max_sweeps, int flags, uint8_t* warped, int64_t* counts, void* ws, unet_stream_t stream);
+void unet_simple_point_table(uint8_t out[256]);
+
 /* Tuning hooks, process-global:
  *  "autotune"      1 (default, or env UNET_AUTOTUNE) = the plan times the
  *                  applicable GEMM variants (tile shape, split-K, wgrad pixel

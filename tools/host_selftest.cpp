@@ -242,6 +242,39 @@ static void test_ctc() {
   unet_ctc_destroy(nullptr);
 }
 
+// the warping error's host side: the simple-point table and the argument checks
+// (no launch: every call here is refused first)
+static void test_warp() {
+  uint8_t t[256];
+  unet_simple_point_table(t);
+  int ones = 0;
+  for (int c = 0; c < 256; ++c) {
+    CHECK(t[c] <= 1);
+    ones += t[c];
+  }
+  CHECK(ones == 116);
+  CHECK(t[0] == 0 && t[255] == 0);     // an isolated pixel, an interior pixel
+  CHECK(t[1] == 1 && t[2] == 1);       // the end of a line, straight or diagonal
+  CHECK(t[0x11] == 0);                 // N and S only: the pixel is a bridge
+  CHECK(t[0x05] == 1 && t[0x07] == 1);  // N and E stay joined through their diagonal, with or without NE
+  CHECK(t[0x55] == 0 && t[0xAA] == 0);  // the four edge neighbours, the four corners
+  CHECK(unet_warping_error_ws_bytes(0, 4, 4) == 0 && unet_warping_error_ws_bytes(1, 0, 4) == 0 &&
+        unet_warping_error_ws_bytes(1, 4, -1) == 0 && unet_warping_error_ws_bytes(1 << 16, 1 << 15, 1) == 0);
+  const size_t one = unet_warping_error_ws_bytes(1, 512, 512);
+  CHECK(one >= 4u * 514 * 18 * 4 && one % 256 == 0 && unet_warping_error_ws_bytes(3, 512, 512) >= 3 * (one - 255));
+  uint16_t g[4] = {0, 1, 1, 0};
+  uint8_t p[4] = {0, 1, 0, 0};
+  int64_t c5[5];
+  CHECK(unet_warping_error(g, p, 0, 2, 2, 4, 1, 0, 0, nullptr, c5, nullptr, nullptr) == -EINVAL);
+  CHECK(unet_warping_error(g, p, 1, 2, 2, -2, 1, 0, 0, nullptr, c5, nullptr, nullptr) == -EINVAL);
+  CHECK(unet_warping_error(g, p, 1, 2, 2, 256, 1, 0, 0, nullptr, c5, nullptr, nullptr) == -EINVAL);
+  CHECK(unet_warping_error(g, p, 1, 2, 2, 4, 1, -1, 0, nullptr, c5, nullptr, nullptr) == -EINVAL);
+  CHECK(unet_warping_error(g, p, 1 << 16, 1 << 15, 1, 4, 1, 0, 0, nullptr, c5, nullptr, nullptr) == -EINVAL);
+  CHECK(unet_warping_error(nullptr, p, 1, 2, 2, 4, 1, 0, 0, nullptr, c5, nullptr, nullptr) == -EINVAL);
+  CHECK(unet_warping_error(g, p, 1, 2, 2, 4, 1, 0, UNET_WARP_FORCE_WS, nullptr, c5, nullptr, nullptr) == -EINVAL);  // no workspace
+  CHECK(std::strstr(unet_last_error(), "unet_warping_error") != nullptr);
+}
+
 static void test_misc() {
   CHECK(std::strlen(unet_version()) > 0);
   const size_t need = unet_tuning_report(nullptr, 0);
@@ -511,6 +544,7 @@ int main(int argc, char** argv) {
   test_lsap();
   test_tracker();
   test_ctc();
+  test_warp();
   test_misc();
   if (argc > 1) test_selection(argv[1], argc > 2 && std::strcmp(argv[2], "--record") == 0);
   else CHECK(!"usage: host_selftest tests/golden/gemm_selection.txt [--record]");

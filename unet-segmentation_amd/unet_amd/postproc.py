@@ -1,11 +1,16 @@
 """Post-processing on the GPU (utils/metrics.py): instance labelling of
-predicted masks and the Rand index, behind unet_instance_masks /
-unet_rand_index (include/unet_hip.h).
+predicted masks, the Rand index, and the warping and pixel error, behind
+unet_instance_masks / unet_rand_index / unet_warping_error (include/unet_hip.h).
 
     labels = instance_masks(mask_u8, min_size=15)   # get_instance_masks (:42-72), uint16
     ri, re = rand_index(gt_labels, labels)           # calculate_rand_index_and_error (:75-139)
+    r = warping_error(gt_labels, mask_u8, radius=4)  # the calculate_warping_error placeholder
+    r.warping_error, r.pixel_error                   # fractions of H W per frame, on the device
 """
 from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional
 
 import torch
 
@@ -54,3 +59,85 @@ def rand_index(gt: torch.Tensor, pred: torch.Tensor):
                                    _lib.stream_of()), "unet_rand_index")
     ri, re = out.tolist()
     return ri, re
+
+
+FORCE_WS = 1  # UNET_WARP_FORCE_WS: keep the bit planes in the workspace (tests)
+
+
+@dataclass
+class WarpingResult:
+    """Per-frame results of warping_error, all on the device: `counts` is
+    (N, 5) int64 = pixel error, warping error, flips, sweeps, converged (a (5,)
+    row for an (H, W) input); the properties read its columns, the errors as
+    the fractions of H W the ISBI tables quote."""
+    counts: torch.Tensor
+    pixels: int
+    warped: Optional[torch.Tensor] = None
+
+    @property
+    def pixel_error_count(self):
+        return self.counts[..., 0]
+
+    @property
+    def warping_error_count(self):
+        return self.counts[..., 1]
+
+    @property
+    def flips(self):
+        return self.counts[..., 2]
+
+    @property
+    def sweeps(self):
+        return self.counts[..., 3]
+
+    @property
+    def converged(self):
+        return self.counts[..., 4] != 0
+
+    @property
+    def pixel_error(self):
+        return self.counts[..., 0].double() / self.pixels
+
+    @property
+    def warping_error(self):
+        return self.counts[..., 1].double() / self.pixels
+
+
+def warping_error(gt: torch.Tensor, pred: torch.Tensor, radius: int = 4, separate: bool = True, max_sweeps: int = 0,
+                  return_warped: bool = False, flags: int = 0) -> WarpingResult:
+    """Warping error of a binary prediction against instance ground truth:
+    gt (N, H, W) or (H, W) instance ids (< 65536), pred of the same shape with
+    > 0 = foreground, both on the HIP device.  The ground truth -- with a
+    background ridge between touching cells when `separate` -- is warped onto
+    the prediction by flipping simple points within `radius` of its boundary
+    (-1 = anywhere, 0 = nowhere) until none is left or `max_sweeps` sweeps ran
+    (0 = no limit); what still differs is the warping error, the topological
+    part of the pixel error (include/unet_hip.h has the exact schedule).  The
+    counts stay on the device until they are read."""
+    if gt.shape != pred.shape or gt.dim() not in (2, 3):
+        raise ValueError("gt and pred must be (H, W) or (N, H, W) of the same shape")
+    if gt.device.type != "cuda" or pred.device.type != "cuda":
+        raise ValueError("warping_error runs on the HIP device only (no CPU fallback)")
+    squeeze = gt.dim() == 2
+    g = _u16(gt[None] if squeeze else gt)
+    p = ((pred[None] if squeeze else pred) > 0).to(torch.uint8).contiguous()
+    n, h, w = g.shape
+    lib = _lib.load()
+    ws = torch.empty(lib.unet_warping_error_ws_bytes(n, h, w), dtype=torch.uint8, device=g.device)
+    counts = torch.empty((n, 5), dtype=torch.int64, device=g.device)
+    warped = torch.empty((n, h, w), dtype=torch.uint8, device=g.device) if return_warped else None
+    _lib.check(lib.unet_warping_error(g.data_ptr(), p.data_ptr(), n, h, w, int(radius), 1 if separate else 0,
+                                      int(max_sweeps), int(flags), _lib.ptr(warped), counts.data_ptr(),
+                                      ws.data_ptr(), _lib.stream_of()), "unet_warping_error")
+    if squeeze:
+        counts = counts[0]
+        warped = None if warped is None else warped[0]
+    return WarpingResult(counts, h * w, warped)
+
+
+def pixel_error(gt: torch.Tensor, pred: torch.Tensor, separate: bool = True) -> torch.Tensor:
+    """Pixels at which the binary ground truth of warping_error (gt > 0, with
+    the background ridge between touching cells when `separate`) differs from
+    pred > 0: an int64 count per frame, on the device (divide by H W for the
+    fraction)."""
+    return warping_error(gt, pred, radius=0, separate=separate).pixel_error_count
