@@ -532,6 +532,15 @@ void unet_simple_point_table(uint8_t out[256]);
  *                  (70, 71) run k_igemm_plane (LDS-DMA ring) where their tile
  *                  has one (1, 2, 3, 8, 9; see unet_igemm_plane_launches);
  *                  0 = k_igemm (bit-identical results for the same tile).
+ *  "wino_persist"  1 (default; env UNET_WINO_PERSIST) = the fused fp32 Winograd
+ *                  tiles 76 and 75 run their persistent form: one workgroup
+ *                  per CU walks the tile groups, claimed through counters in
+ *                  the workspace, and loads the next group's first operands
+ *                  under the current group's output stage (see
+ *                  unet_wino_persist_launches); 0 = one workgroup per group
+ *                  (bit-identical results).
+ *  "wino_persist_wgs" n (tests; default -1 = one per CU): workgroups of the
+ *                  persistent form's grid.
  *  "wino_point_tile" id (tests; default -1 = off): the unfused Winograd tiles
  *                  run their point GEMMs on register-staged tile id (1-4, 6-9)
  *                  where it fits, instead of the tuned or heuristic one.
@@ -575,6 +584,11 @@ long long unet_wgrad_oihw_sites(int reset);
  * of this implementation's schedule (models/unet_model.py:11,15 is the Conv2d
  * those GEMMs compute). */
 long long unet_igemm_plane_launches(int reset);
+/* Launches of the fused fp32 Winograd tiles 76 / 75 in their persistent form
+ * (unet_set_tuning "wino_persist"); reset != 0 also zeroes the count.  A counter
+ * of this implementation's schedule (models/unet_model.py:11,15 is the Conv2d
+ * those kernels compute). */
+long long unet_wino_persist_launches(int reset);
 /* Tuning database (cf. MIOpen's perf-db): unet_tuning_save writes every tuned
  * choice as "key<TAB>tile<TAB>split" lines (returns the count or -errno);
  * unet_tuning_load merges such a file, overriding equal keys (returns the

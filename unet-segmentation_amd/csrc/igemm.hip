@@ -1294,8 +1294,8 @@ static hipError_t go_tile(const IgemmArgs& a, hipStream_t s, int tile) {
   return t ? t->go(a, s) : hipErrorInvalidValue;
 }
 
-static bool igemm_args_ok(const IgemmArgs& a) {
-  return a.M > 0 && a.N > 0 && a.K > 0 && (a.K % 16) == 0 && (a.a.Cg % 16) == 0 && (a.a.c_split % 16) == 0;
+static bool igemm_args_ok(const IgemmArgs& a, int q = 16) {
+  return a.M > 0 && a.N > 0 && a.K > 0 && (a.K % q) == 0 && (a.a.Cg % q) == 0 && (a.a.c_split % q) == 0;
 }
 
 // Built-in tile choice (used when no tuned choice exists), measured per U-Net
@@ -1334,8 +1334,15 @@ int igemm_heuristic_tile(const IgemmArgs& a) {
   return -1;
 }
 
+// a forced fused F(2x2) tile (75, 77; tests) works in 8-channel chunks and holds
+// its own channel rule (wino_fused2_applies)
+static int igemm_forced_quantum(const IgemmArgs& a) {
+  const IgemmTile* t = igemm_tile(resolve_forced_igemm(a, g_tune_igemm).tile);
+  return t && t->family == IgemmFamily::WinoFused && t->wino_m == 2 ? 8 : 16;
+}
+
 hipError_t launch_igemm(const IgemmArgs& a0, hipStream_t s) {
-  if (!igemm_args_ok(a0)) return hipErrorInvalidValue;
+  if (!igemm_args_ok(a0, igemm_forced_quantum(a0))) return hipErrorInvalidValue;
   IgemmArgs a = a0;
   a.ksplit = 1;
   return go_tile(a, s, igemm_heuristic_tile(a));

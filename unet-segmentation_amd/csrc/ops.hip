@@ -79,7 +79,8 @@ extern "C" {
 // transformed weights of the fused Winograd tiles (72, 73, 75, 76) for forced
 // per-op GEMMs (tests: unet_set_tuning("igemm_variant", t)); the built-in
 // choice of the per-op entry points never takes a Winograd tile
-static size_t op_wino_bytes(int ci, int co) { return al256(sizeof(float) * 36 * (size_t)ci * co); }
+// (+ 256 B: the claim counters of the persistent forms, behind V)
+static size_t op_wino_bytes(int ci, int co) { return al256(sizeof(float) * 36 * (size_t)ci * co) + 256; }
 static size_t op_wgrad_wino_bytes(int n, int h, int w, int ci, int co);
 static size_t op_wgrad_extra_bytes(int n, int h, int w, int ci, int co);
 // A forced unfused Winograd tile (70, 71: U, M and V in HBM) borrows the scratch
@@ -127,7 +128,10 @@ size_t unet_conv_ws_bytes(int n, int h, int w, int ci, int co) {
 
 int unet_conv3x3_fwd(const float* x, int n, int h, int w, int ci, const float* wt, const float* bias, int co,
                      const float* xs, const float* xb, float* y, void* ws, unet_stream_t st) {
-  if (ci % 16 || co % 64 || h < 3 || w < 3) return -EINVAL;
+  // ci % 16; 8 more channels only for a forced fp32 tile that takes them (the
+  // fused F(2x2) tiles' single-chunk case, tests)
+  if (ci % 8 || co % 64 || h < 3 || w < 3) return -EINVAL;
+  if (ci % 16 && (g_op_prec != UNET_PREC_FP32 || g_tune_igemm <= 0)) return -EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(st);
   float* wf = reinterpret_cast<float*>(ws);
   OPCK(launch_pack_conv(wt, co, ci, 3, 3, wf, nullptr, s));
@@ -161,6 +165,7 @@ int unet_conv3x3_fwd(const float* x, int n, int h, int w, int ci, const float* w
   a.e.bias = bias;
   a.e.d[0] = Dst{y, h - 2, w - 2, co, 0, 0};
   op_set_wino(a, ws, n, h, w, ci, co);
+  if (ci % 16 && resolve_forced_igemm(a, g_tune_igemm).tile < 0) return -EINVAL;
   OPCK(op_b_to_bf16(a, 9 * (size_t)ci * co, reinterpret_cast<char*>(ws) + al256(sizeof(float) * 9 * (size_t)ci * co),
                     s));
   OPCK(launch_igemm(a, s));
@@ -169,7 +174,8 @@ int unet_conv3x3_fwd(const float* x, int n, int h, int w, int ci, const float* w
 
 int unet_conv3x3_dgrad(const float* dy, int n, int h, int w, int ci, const float* wt, int co, float* dx, void* ws,
                        unet_stream_t st) {
-  if (ci % 64 || co % 16 || h < 3 || w < 3) return -EINVAL;
+  if (ci % 64 || co % 8 || h < 3 || w < 3) return -EINVAL;  // co % 16, or 8 more as unet_conv3x3_fwd's ci
+  if (co % 16 && (g_op_prec != UNET_PREC_FP32 || g_tune_igemm <= 0)) return -EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(st);
   char* p = reinterpret_cast<char*>(ws);
   const size_t wb = al256(sizeof(float) * 9 * (size_t)ci * co);
@@ -202,6 +208,7 @@ int unet_conv3x3_dgrad(const float* dy, int n, int h, int w, int ci, const float
   a.K = 9 * co;
   a.e.d[0] = Dst{dx, h, w, ci, 0, 0};
   op_set_wino(a, ws, n, h, w, ci, co);
+  if (co % 16 && resolve_forced_igemm(a, g_tune_igemm).tile < 0) return -EINVAL;
   OPCK(op_b_to_bf16(a, 9 * (size_t)ci * co, wf, s));
   OPCK(launch_igemm(a, s));
   return 0;
@@ -591,6 +598,8 @@ int unet_set_tuning(const char* key, int value) {
   else if (k == "wgrad_plane") g_wgrad_plane = value;
   else if (k == "wgrad_oihw") g_wgrad_oihw = value;
   else if (k == "igemm_plane") g_igemm_plane = value;
+  else if (k == "wino_persist") g_wino_persist = value;
+  else if (k == "wino_persist_wgs") g_wino_persist_wgs = value;
   else if (k == "wino_point_tile") g_wino_point_tile = value;
   else if (k == "ctc_chunk_frames" || k == "ctc_dense_cells") {  // ctc.hip clamps them to what it supports
     if (value < -1 || (value == 0 && k == "ctc_chunk_frames")) return -EINVAL;  // -1 = the default

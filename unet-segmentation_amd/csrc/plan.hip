@@ -1603,6 +1603,10 @@ long long unet_fused_bnb_sites(int reset) {
 long long unet_wgrad_oihw_sites(int reset) {
   return reset ? unet::g_wgrad_oihw_sites.exchange(0) : unet::g_wgrad_oihw_sites.load();
 }
+long long unet_wino_persist_launches(int reset) {
+  return reset ? unet::g_wino_persist_launches.exchange(0) : unet::g_wino_persist_launches.load();
+}
+
 long long unet_igemm_plane_launches(int reset) {
   return reset ? unet::g_igemm_plane_launches.exchange(0) : unet::g_igemm_plane_launches.load();
 }

@@ -122,6 +122,9 @@ extern int g_wgrad_plane;    // wgrad_plane.hip: batched fp32 point GEMMs on the
 extern int g_wgrad_oihw;     // plan.hip: Winograd weight gradients store torch's OIHW layout themselves
 extern int g_igemm_plane;    // igemm_plane.hip: batched fp32 forward / dgrad point GEMMs on the LDS-DMA ring kernel
 extern std::atomic<long long> g_igemm_plane_launches;  // k_igemm_plane launches (unet_igemm_plane_launches)
+extern int g_wino_persist;      // winograd.hip: tiles 76 / 75 in their persistent form (1) or the plain one (0)
+extern int g_wino_persist_wgs;  // workgroups of the persistent grid (tests; -1 = one per CU)
+extern std::atomic<long long> g_wino_persist_launches;  // persistent launches (unet_wino_persist_launches)
 extern int g_wino_point_tile;  // winograd.hip: forced tile of launch_wino's point GEMMs (tests), -1 = off
 extern std::atomic<long long> g_nondet_sites;
 

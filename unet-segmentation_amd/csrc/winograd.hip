@@ -24,6 +24,7 @@
 // order (tests/test_gpu_ops.py, tests/test_gpu_model.py force tile 70).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "gemm_common.h"
 #include "ring_common.h"
@@ -1210,8 +1211,70 @@ hipError_t launch_wino_fused(const IgemmArgs& a, hipStream_t s) {
 // there: 3e8 conflict cycles per step, profiles/r03_pmc_summary_fp32.txt)
 __device__ __forceinline__ int wf8_slot(int row, int q) { return (q ^ ((row >> 2) & 3)) << 1; }
 
-__global__ void k_wino4f_w8(const float* __restrict__ b, int N, int Cg, float* __restrict__ v) {
+// ---------------------------------------------------------------------------
+// Persistent forms of the register-output fused kernels (tiles 76, 75;
+// unet_set_tuning "wino_persist"): min(groups, CUs) workgroups walk the G tile
+// groups (a group = what one workgroup of the plain form computes; its id is
+// the plain form's remapped block id, so column block, tile base and
+// statistics slot -- every addend -- are the plain form's).  Groups are claimed
+// through eight counters in the workspace, one per XCD stretch
+// [x G / 8, (x + 1) G / 8) (the plain form's XCD locality); a workgroup whose
+// own stretch is empty takes from the next ones, so one that starts late (the
+// weight-gradient stream shares the CUs) simply ends up with fewer groups.
+// Workgroup b starts on index b >> 3 of stretch b & 7 without a claim; the
+// weight-transform launch that precedes the kernel sets counter x to the
+// number of workgroups of that XCD (no memset node, no extra launch).
+// ---------------------------------------------------------------------------
+constexpr int kWinoPersistCtrs = 8;
+__device__ __forceinline__ unsigned wp_ctr_init(unsigned pgrid, int x) { return (pgrid + 7u - (unsigned)x) >> 3; }
+__device__ __forceinline__ void wp_stretch(unsigned G, int x, unsigned& lo, unsigned& hi) {
+  lo = (unsigned)(((unsigned long long)G * (unsigned)x) >> 3);
+  hi = (unsigned)(((unsigned long long)G * (unsigned)(x + 1)) >> 3);
+}
+// the group of index k in stretch x, else the next unclaimed group of the
+// other stretches; -1: none is left.  One thread per workgroup calls this.
+__device__ __forceinline__ int wp_resolve(unsigned* ctr, unsigned G, int x, unsigned k) {
+  unsigned lo, hi;
+  wp_stretch(G, x, lo, hi);
+  if (k < hi - lo) return (int)(lo + k);
+  for (int i = 1; i < 8; ++i) {
+    const int s = (x + i) & 7;
+    wp_stretch(G, s, lo, hi);
+    if (hi == lo) continue;
+    k = atomicAdd(ctr + s, 1u);
+    if (k < hi - lo) return (int)(lo + k);
+  }
+  return -1;
+}
+// the plain form's blockIdx.x of group gid (its statistics slot is blockIdx.x % kStatGroups)
+__device__ __forceinline__ unsigned wp_block_of(unsigned G, unsigned gid) {
+  if (G & 7u) return gid;
+  const unsigned q = G >> 3;
+  return (gid % q) * 8u + gid / q;
+}
+// the loader's patch of tile t: image, tile row / column and the rows / columns
+// of its (MT + 2)^2 window inside the gather's input grid (0 past the last tile)
+struct WfPatch {
+  int img, ty, tx, vrows, vcols;
+};
+template <int MT, class TI>
+__device__ __forceinline__ WfPatch wf_patch(TI t, TI T, int Th, int Tw, int Hg, int Wg) {
+  WfPatch p{0, 0, 0, 0, 0};
+  if (t < T) {
+    p.tx = (int)(t % (TI)Tw);
+    const TI r = t / (TI)Tw;
+    p.ty = (int)(r % (TI)Th);
+    p.img = (int)(r / (TI)Th);
+    p.vrows = min(MT + 2, Hg + 2 - MT * p.ty);
+    p.vcols = min(MT + 2, Wg + 2 - MT * p.tx);
+  }
+  return p;
+}
+
+__global__ void k_wino4f_w8(const float* __restrict__ b, int N, int Cg, float* __restrict__ v, unsigned* ctr,
+                            unsigned pgrid) {
   const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (ctr && i < kWinoPersistCtrs) ctr[i] = wp_ctr_init(pgrid, (int)i);  // the persistent form's claim counters
   if (i >= (long long)N * Cg) return;
   const int n = (int)(i / Cg), c = (int)(i - (long long)n * Cg);
   float tg[6][3];
@@ -1255,21 +1318,26 @@ __device__ __forceinline__ float wf_epi(float v, float yv, float sc, float sh, f
 // 4 mq .. +3 of tile t0 + 16 th + mi; A^T M A from registers, the epilogue
 // (bias, dgrad ReLU mask + BN-backward statistics or forward sums), 16-B
 // stores.  `lds` is free (every wave past the chunk loop's last barrier).
+// FWD (the launcher's e.yref == nullptr): the forward's stage without the mask
+// compare, the BN-backward coefficients and the y staging.  TI: the tile index
+// type (unsigned in the persistent form, whose launcher bounds T).  grp: the
+// statistics slot.
+template <bool FWD, class TI>
 __device__ __forceinline__ void wf64_output(const floatx4 (&acc)[36], const Gather& g, const Epilogue& e, int N,
-                                            long long T, int Th, int Tw, long long t0, int n0, int th, int cb,
-                                            int mi, int mq, int lane, int wave, float* lds) {
-  const long long tt = t0 + 16 * th + mi;
+                                            TI T, int Th, int Tw, TI t0, int n0, int th, int cb,
+                                            int mi, int mq, int lane, int wave, float* lds, int grp) {
+  const TI tt = t0 + (TI)(16 * th + mi);
   const int col0 = n0 + 16 * cb + 4 * mq;
   const bool second = col0 >= e.n_split;  // uniform per 16-channel block (n_split % 16 == 0)
   float* dptr = second ? e.d[1].ptr : e.d[0].ptr;
   const int dC = second ? e.d[1].C : e.d[0].C;
   const int dcol = second ? col0 - e.n_split : col0;
-  const bool bwd_mask = e.yref != nullptr && !second;
+  const bool bwd_mask = !FWD && e.yref != nullptr && !second;
   float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
   if (tt < T) {
-    const int ox = (int)(tt % Tw);
-    const long long rq = tt / Tw;
-    const int oy = (int)(rq % Th), on = (int)(rq / Th);
+    const int ox = (int)(tt % (TI)Tw);
+    const TI rq = tt / (TI)Tw;
+    const int oy = (int)(rq % (TI)Th), on = (int)(rq / (TI)Th);
     float o[4][4][4];  // [channel][row][col]
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -1341,7 +1409,6 @@ __device__ __forceinline__ void wf64_output(const floatx4 (&acc)[36], const Gath
       s2[r] += __shfl_xor(s2[r], o2);
     }
   if (mi == 0) {
-    const int grp = blockIdx.x % kStatGroups;
     const int nsplit = e.n_split < N ? e.n_split : N;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -1528,7 +1595,8 @@ __global__ __launch_bounds__(512, 1) void k_wino4f64(Gather g, const float* __re
     return;
   }
 
-  wf64_output(acc, g, e, N, T, Th, Tw, t0, n0, th, cb, mi, mq, lane, wave, lds);
+  wf64_output<false, long long>(acc, g, e, N, T, Th, Tw, t0, n0, th, cb, mi, mq, lane, wave, lds,
+                                (int)(blockIdx.x % kStatGroups));
 }
 
 bool wino_fused64_applies(const IgemmArgs& a) {
@@ -1546,7 +1614,8 @@ hipError_t launch_wino_fused64(const IgemmArgs& a, hipStream_t s) {
   const long long nw = (long long)a.N * g.Cg;
   const int NB = a.N / 64;
   const long long G = (T + 31) / 32 * NB;
-  hipLaunchKernelGGL(k_wino4f_w8, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, a.b, a.N, g.Cg, V);
+  hipLaunchKernelGGL(k_wino4f_w8, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, a.b, a.N, g.Cg, V,
+                     (unsigned*)nullptr, 0u);
   static const int abl = ablation_env("UNET_WF64_ABL");
   switch (abl) {
 #define WF64(A) \
@@ -1590,42 +1659,96 @@ hipError_t launch_wino_fused64(const IgemmArgs& a, hipStream_t s) {
 // ---------------------------------------------------------------------------
 constexpr int kWf64pMaxCg = 1024;
 
+// PERSIST: the persistent form (see wp_resolve).  Per group it differs from the
+// plain form in three places: the last chunk issues the NEXT group's raw(0) and
+// VA(0) where the plain form re-issues its own transfers (same counts), so they
+// land during the output stage; VB(0) of the next group is issued after the
+// output stage (the dgrad stages its mask operand in U and VB, which is why VB
+// follows U here; VB is first read after chunk 0's half-A MFMAs); and the
+// output stage's transfers sit between VA(0) and VB(0) in the in-order vmcnt
+// queue, which only makes the loop's counted waits wait for more.  The
+// BatchNorm table is filled once per workgroup.  G: the number of groups.
+template <bool PERSIST, bool FWD>
 __global__ __launch_bounds__(512, 1) void k_wino4f64p(Gather g, const float* __restrict__ V, int N, long long T,
-                                                      int Th, int Tw, int NB, Epilogue e) {
+                                                      int Th, int Tw, int NB, Epilogue e, unsigned G,
+                                                      unsigned* __restrict__ ctr) {
   constexpr int PU = 32 * 8 + 8, PV = 64 * 8;
   constexpr int PA = 16;  // points of V half A
   constexpr int U_F = 36 * PU, VA_F = PA * PV, VB_F = (36 - PA) * PV, RAW_F = 8 * 18 * 64;
   __shared__ __attribute__((aligned(16))) float lds[U_F + VA_F + VB_F + RAW_F + 2 * kWf64pMaxCg];
+  __shared__ int sclaim[3];  // PERSIST: [0] a stolen first group, [1 + (i & 1)] the group after the i-th
   float* Us = lds;
-  float* VAs = lds + U_F;
-  float* VBs = VAs + VA_F;
-  float* raws = VBs + VB_F;
+  float* VBs = lds + U_F;  // U | VB: the 64 KB the dgrad output stage reuses hold nothing prefetched
+  float* VAs = VBs + VB_F;
+  float* raws = VAs + VA_F;
   float* ss = raws + RAW_F;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  long long bid = blockIdx.x;
-  const long long G = gridDim.x;
-  if ((G & 7) == 0) bid = (bid & 7) * (G >> 3) + (bid >> 3);  // an XCD's workgroups share tiles
-  const int nb = (int)(bid % NB);
-  const long long t0 = (bid / NB) * 32;
-  const int n0 = nb * 64;
+  static_assert((U_F + VB_F) * 4 >= 8 * 8192, "mask operand staging");
+  const int tid = threadIdx.x;
+  using TI = typename std::conditional<PERSIST, unsigned, long long>::type;
   const int Cg = g.Cg, nk = Cg >> 3;
+  // the per-lane roles.  PERSIST derives them again at the top of every group
+  // (from a thread index the compiler cannot see through), so that none of
+  // them is held in a register across the output stage
+  int lane, wave, hf, lt, lc, th, cb, mi, mq, aoff, boff;
+  float* ubase;
+  unsigned raw_lds;
+  WfPatch pc;
+  bool wfc;
 
-  // ---- loader role: patch (tile lt, channel lc), column half hf (tile 73) ----
-  const int hf = (lane >> 4) & 1;
-  const int pt = wave * 32 + (lane & 15) + ((lane >> 5) << 4);
-  const int lt = pt >> 3, lc = pt & 7;
-  const long long t = t0 + lt;
-  int img = 0, ty = 0, tx = 0;
-  if (t < T) {
-    tx = (int)(t % Tw);
-    const long long r = t / Tw;
-    ty = (int)(r % Th);
-    img = (int)(r / Th);
+  // ---- this workgroup's first group ----
+  TI t0;
+  int n0, grp;
+  const int xcd = blockIdx.x & 7;
+  unsigned kfire = 0;
+  if constexpr (PERSIST) {
+    unsigned lo, hi;
+    wp_stretch(G, xcd, lo, hi);
+    const unsigned k0 = blockIdx.x >> 3;
+    int gid;
+    if (k0 < hi - lo) {
+      gid = (int)(lo + k0);
+    } else {  // more workgroups than groups in this stretch
+      if (tid == 0) sclaim[0] = wp_resolve(ctr, G, xcd, k0);
+      __syncthreads();
+      gid = sclaim[0];
+      if (gid < 0) return;
+    }
+    gid = __builtin_amdgcn_readfirstlane(gid);
+    if (tid == 0) kfire = atomicAdd(ctr + xcd, 1u);  // the group after: resolved below, behind the first DMAs
+    n0 = (int)((unsigned)gid % (unsigned)NB) * 64;
+    t0 = (unsigned)gid / (unsigned)NB * 32u;
+    grp = (int)(wp_block_of(G, (unsigned)gid) % kStatGroups);
+  } else {
+    long long bid = blockIdx.x;
+    const long long Gd = gridDim.x;
+    if ((Gd & 7) == 0) bid = (bid & 7) * (Gd >> 3) + (bid >> 3);  // an XCD's workgroups share tiles
+    n0 = (int)(bid % NB) * 64;
+    t0 = (bid / NB) * 32;
+    grp = (int)(blockIdx.x % kStatGroups);
   }
-  const int vrows = t < T ? min(6, g.Hg + 2 - 4 * ty) : 0;
-  const int vcols = t < T ? min(6, g.Wg + 2 - 4 * tx) : 0;
-  const bool wfull = __all(vrows == 6 && vcols == 6);
-  float* const ubase = Us + (3 * hf) * 6 * PU + lt * 8 + wf8_slot(lt, lc & 3) + (lc >> 2);
+
+  auto roles = [&]() {
+    int tv = tid;
+    if constexpr (PERSIST) asm volatile("" : "+v"(tv));
+    lane = tv & 63;
+    wave = tv >> 6;
+    // ---- loader role: patch (tile lt, channel lc), column half hf (tile 73) ----
+    hf = (lane >> 4) & 1;
+    const int pt = wave * 32 + (lane & 15) + ((lane >> 5) << 4);
+    lt = pt >> 3;
+    lc = pt & 7;
+    pc = wf_patch<4, TI>(t0 + (TI)lt, (TI)T, Th, Tw, g.Hg, g.Wg);
+    wfc = __all(pc.vrows == 6 && pc.vcols == 6);
+    ubase = Us + (3 * hf) * 6 * PU + lt * 8 + wf8_slot(lt, lc & 3) + (lc >> 2);
+    raw_lds = (unsigned)(size_t)(lds_u8_t*)raws + (unsigned)wave * (18u * 256u);
+    // ---- MFMA role: wave = (tile half th, 16-channel block cb), all 36 points (tile 73) ----
+    th = wave & 1;
+    cb = wave >> 1;
+    mi = lane & 15;
+    mq = lane >> 4;
+    aoff = (16 * th + mi) * 8 + wf8_slot(16 * th + mi, mq);
+    boff = (16 * cb + mi) * 8 + wf8_slot(mi, mq);
+  };
 
   // the consumer BatchNorm+ReLU table (scale | shift) of the concatenated channels
   const bool tf0 = g.s[0].scale != nullptr, tf1 = g.c_split < Cg && g.s[1].scale != nullptr;
@@ -1640,15 +1763,15 @@ __global__ __launch_bounds__(512, 1) void k_wino4f64p(Gather g, const float* __r
     }
   }
 
-  const unsigned raw_lds = (unsigned)(size_t)(lds_u8_t*)raws + (unsigned)wave * (18u * 256u);
-  auto issue_raw = [&](int kc) {  // 18 dword DMAs: raw[yy][xx] -> raw area row yy * 3 + xx
+  // 18 dword DMAs of chunk kc of patch p: raw[yy][xx] -> raw area row yy * 3 + xx
+  auto issue_raw = [&](const WfPatch& p, bool wfull, int kc) {
     const bool second = kc * 8 >= g.c_split;  // c_split % 8 == 0: uniform source
     const unsigned long long sb = uniform_u64(second ? g.s[1].ptr : g.s[0].ptr);
     const int sH = second ? g.s[1].H : g.s[0].H, sW = second ? g.s[1].W : g.s[0].W;
     const int sC = second ? g.s[1].C : g.s[0].C;
     const int soy = second ? g.s[1].oy : g.s[0].oy, sox = second ? g.s[1].ox : g.s[0].ox;
     const int cl = kc * 8 - (second ? g.c_split : 0) + lc;
-    const unsigned o0 = ((unsigned)((img * sH + 4 * ty + soy) * sW + 4 * tx + sox) * sC + cl) * 4u;
+    const unsigned o0 = ((unsigned)((p.img * sH + 4 * p.ty + soy) * sW + 4 * p.tx + sox) * sC + cl) * 4u;
     const unsigned rs = (unsigned)sW * sC * 4u, cs = (unsigned)sC * 4u;
     if (wfull) {
       const unsigned oh = o0 + 3u * hf * cs;
@@ -1657,7 +1780,7 @@ __global__ __launch_bounds__(512, 1) void k_wino4f64p(Gather g, const float* __r
 #pragma unroll
         for (int xx = 0; xx < 3; ++xx) dma4_sv(oh + (yy * rs + xx * cs), sb, raw_lds + (yy * 3 + xx) * 256u);
     } else {  // clamp to the last in-window row / column (zeroed in commit)
-      const unsigned lr = (unsigned)max(vrows - 1, 0), lcn = (unsigned)max(vcols - 1, 0);
+      const unsigned lr = (unsigned)max(p.vrows - 1, 0), lcn = (unsigned)max(p.vcols - 1, 0);
 #pragma unroll
       for (int yy = 0; yy < 6; ++yy)
 #pragma unroll
@@ -1671,25 +1794,26 @@ __global__ __launch_bounds__(512, 1) void k_wino4f64p(Gather g, const float* __r
   // 16-35, 40 pieces, 5 per wave
   const unsigned long long vbase = uniform_u64(V);
   const unsigned va_lds = (unsigned)(size_t)(lds_u8_t*)VAs, vb_lds = (unsigned)(size_t)(lds_u8_t*)VBs;
-  auto issue_v = [&](int kc, int half) {
+  auto issue_v = [&](int nn0, int kc, int half) {
     const int np = half ? 5 : 4, p0 = half ? PA : 0;
     const unsigned dst = half ? vb_lds : va_lds;
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
       if (j < np) {
-        const int pc = wave + 8 * j;  // piece: point p0 + (pc >> 1), 1-KB half pc & 1
-        dma_sv((unsigned)((((size_t)kc * 36 + p0 + (pc >> 1)) * N + n0) * 32) + (unsigned)((pc & 1) * 1024 + lane * 16),
-               vbase, dst + (unsigned)((pc >> 1) * PV * 4 + (pc & 1) * 1024));
+        const int pc2 = wave + 8 * j;  // piece: point p0 + (pc2 >> 1), 1-KB half pc2 & 1
+        dma_sv((unsigned)((((size_t)kc * 36 + p0 + (pc2 >> 1)) * N + nn0) * 32) + (unsigned)((pc2 & 1) * 1024 + lane * 16),
+               vbase, dst + (unsigned)((pc2 >> 1) * PV * 4 + (pc2 & 1) * 1024));
       }
     }
   };
-  auto commit = [&](int kc) {
+  // chunk kc of patch p into U; the raw area is refilled with chunk kn of patch pn
+  auto commit = [&](int kc, const WfPatch& p, bool wfull, const WfPatch& pn, bool wfn, int kn) {
     vm_wait<9>();  // raw(kc) landed (VA(kc), VB(kc) may still be in flight)
     float raw[18];
 #pragma unroll
     for (int q = 0; q < 18; ++q) raw[q] = raws[wave * (18 * 64) + q * 64 + lane];
     lgkm_wait0();  // the raw area is read before its refill is issued
-    issue_raw(kc + 1 < nk ? kc + 1 : kc);
+    issue_raw(pn, wfn, kn);
     const bool second = kc * 8 >= g.c_split;
     const bool tf = second ? tf1 : tf0;
     if (tf) {
@@ -1699,7 +1823,7 @@ __global__ __launch_bounds__(512, 1) void k_wino4f64p(Gather g, const float* __r
     }
     if (!wfull) {
 #pragma unroll
-      for (int q = 0; q < 18; ++q) raw[q] = (q / 3 < vrows && 3 * hf + q % 3 < vcols) ? raw[q] : 0.f;
+      for (int q = 0; q < 18; ++q) raw[q] = (q / 3 < p.vrows && 3 * hf + q % 3 < p.vcols) ? raw[q] : 0.f;
     }
 #pragma unroll
     for (int xx = 0; xx < 3; ++xx) {  // columns in place: raw[a][xx] = (B^T d)[a][3 hf + xx]
@@ -1729,53 +1853,123 @@ __global__ __launch_bounds__(512, 1) void k_wino4f64p(Gather g, const float* __r
     }
   };
 
-  // ---- MFMA role: wave = (tile half th, 16-channel block cb), all 36 points (tile 73) ----
-  const int th = wave & 1, cb = wave >> 1;
-  const int mi = lane & 15, mq = lane >> 4;
-  const int aoff = (16 * th + mi) * 8 + wf8_slot(16 * th + mi, mq);
-  const int boff = (16 * cb + mi) * 8 + wf8_slot(mi, mq);
-  floatx4 acc[36];
-#pragma unroll
-  for (int p = 0; p < 36; ++p) acc[p] = (floatx4){0.f, 0.f, 0.f, 0.f};
-
-  __syncthreads();  // BN table
-  issue_raw(0);
-  issue_v(0, 0);
-  issue_v(0, 1);
-  for (int kc = 0; kc < nk; ++kc) {
-    const int kn = kc + 1 < nk ? kc + 1 : kc;
-    commit(kc);
-    vm_wait<23>();  // VA(kc) landed (VB(kc) and raw(kc + 1) may be in flight)
-    lgkm_wait0();   // U stores
-    raw_barrier();
-#pragma unroll
-    for (int p = 0; p < PA; ++p) {
-      const float2 a = *reinterpret_cast<const float2*>(Us + p * PU + aoff);
-      const float2 b = *reinterpret_cast<const float2*>(VAs + p * PV + boff);
-      acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.x, a.x, acc[p], 0, 0, 0);
-      acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.y, a.y, acc[p], 0, 0, 0);
+  if constexpr (!PERSIST) __syncthreads();  // BN table
+  for (int it = 0;; ++it) {
+    roles();
+    if (it == 0) {
+      issue_raw(pc, wfc, 0);
+      issue_v(n0, 0, 0);
+      issue_v(n0, 0, 1);
+      if constexpr (PERSIST) {
+        if (tid == 0) sclaim[1] = wp_resolve(ctr, G, xcd, kfire);
+        __syncthreads();  // BN table, sclaim[1]
+      }
+    } else {
+      issue_v(n0, 0, 1);  // raw(0) and VA(0) came in under the previous group's output stage
     }
-    vm_wait<18>();  // VB(kc) landed (raw(kc + 1) may be in flight)
-    lgkm_wait0();
-    raw_barrier();  // every wave is past its half-A reads
-    issue_v(kn, 0);
+    floatx4 acc[36];
 #pragma unroll
-    for (int p = PA; p < 36; ++p) {
-      const float2 a = *reinterpret_cast<const float2*>(Us + p * PU + aoff);
-      const float2 b = *reinterpret_cast<const float2*>(VBs + (p - PA) * PV + boff);
-      acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.x, a.x, acc[p], 0, 0, 0);
-      acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.y, a.y, acc[p], 0, 0, 0);
+    for (int p = 0; p < 36; ++p) acc[p] = (floatx4){0.f, 0.f, 0.f, 0.f};
+    // what the last chunk prefetches: the next group's chunk 0 (PERSIST, if there is one), else its own again
+    WfPatch pn = pc;
+    bool wfn = wfc;
+    int n0n = n0, gnext = -1;
+    TI t0n = t0;
+    for (int kc = 0; kc < nk; ++kc) {
+      int kn = kc + 1 < nk ? kc + 1 : kc;
+      if constexpr (PERSIST) {
+        if (kc + 1 == nk) {
+          gnext = __builtin_amdgcn_readfirstlane(sclaim[1 + (it & 1)]);
+          if (gnext >= 0) {
+            n0n = (int)((unsigned)gnext % (unsigned)NB) * 64;
+            t0n = (unsigned)gnext / (unsigned)NB * 32u;
+            pn = wf_patch<4, TI>(t0n + (TI)lt, (TI)T, Th, Tw, g.Hg, g.Wg);
+            wfn = __all(pn.vrows == 6 && pn.vcols == 6);
+            kn = 0;
+          }
+        }
+      }
+      commit(kc, pc, wfc, pn, wfn, kn);
+      vm_wait<23>();  // VA(kc) landed (VB(kc) and raw(kn) may be in flight)
+      lgkm_wait0();   // U stores
+      raw_barrier();
+#pragma unroll
+      for (int p = 0; p < PA; ++p) {
+        const float2 a = *reinterpret_cast<const float2*>(Us + p * PU + aoff);
+        const float2 b = *reinterpret_cast<const float2*>(VAs + p * PV + boff);
+        acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.x, a.x, acc[p], 0, 0, 0);
+        acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.y, a.y, acc[p], 0, 0, 0);
+      }
+      vm_wait<18>();  // VB(kc) landed (raw(kn) may be in flight)
+      lgkm_wait0();
+      raw_barrier();  // every wave is past its half-A reads
+      issue_v(n0n, kn, 0);
+#pragma unroll
+      for (int p = PA; p < 36; ++p) {
+        const float2 a = *reinterpret_cast<const float2*>(Us + p * PU + aoff);
+        const float2 b = *reinterpret_cast<const float2*>(VBs + (p - PA) * PV + boff);
+        acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.x, a.x, acc[p], 0, 0, 0);
+        acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.y, a.y, acc[p], 0, 0, 0);
+      }
+      lgkm_wait0();
+      raw_barrier();  // every wave is past its U and half-B reads
+      if (!PERSIST || kc + 1 < nk) issue_v(n0, kn, 1);
     }
-    lgkm_wait0();
-    raw_barrier();  // every wave is past its U and half-B reads
-    issue_v(kn, 1);
+    if constexpr (!PERSIST) {
+      vm_wait<0>();  // the last chunk's re-issued transfers, before the output stage reuses the LDS
+      __syncthreads();
+    } else {
+      if (tid == 0 && gnext >= 0) kfire = atomicAdd(ctr + xcd, 1u);  // the group after the next: lands behind the output stage
+    }
+    wf64_output<FWD, TI>(acc, g, e, N, (TI)T, Th, Tw, t0, n0, th, cb, mi, mq, lane, wave, lds, grp);
+    if constexpr (!PERSIST) {
+      break;
+    } else {
+      if (gnext < 0) {
+        vm_wait<0>();  // the re-issued transfers
+        break;
+      }
+      if (tid == 0) sclaim[1 + ((it + 1) & 1)] = wp_resolve(ctr, G, xcd, kfire);
+      if constexpr (!FWD) {  // every wave has read its staged mask operand before U is rewritten and VB refilled
+        lgkm_wait0();
+        raw_barrier();
+      }
+      t0 = t0n;
+      n0 = n0n;
+      grp = (int)(wp_block_of(G, (unsigned)gnext) % kStatGroups);
+    }
   }
-  vm_wait<0>();  // the last chunk's re-issued transfers, before the output stage reuses the LDS
-  __syncthreads();
-  wf64_output(acc, g, e, N, T, Th, Tw, t0, n0, th, cb, mi, mq, lane, wave, lds);
 }
 
 bool wino_fused64p_applies(const IgemmArgs& a) { return wino_fused64_applies(a) && a.a.Cg <= kWf64pMaxCg; }
+
+// unet_set_tuning("wino_persist", v) / UNET_WINO_PERSIST: 1 runs tiles 76 and 75
+// in their persistent form where wino_persist_applies, 0 the plain form.
+// "wino_persist_wgs" caps the persistent grid (tests; -1 = one workgroup per CU).
+int g_wino_persist = getenv("UNET_WINO_PERSIST") ? atoi(getenv("UNET_WINO_PERSIST")) : 1;
+int g_wino_persist_wgs = -1;
+std::atomic<long long> g_wino_persist_launches{0};
+
+// The persistent form's conditions on a launch of G groups over T tiles with P
+// transform points: 32-bit group and tile arithmetic, and room for the claim
+// counters behind V in the workspace.  Launches of one to four groups per CU
+// keep the plain form: the two such sites of the benchmark (down1.c0 and
+// down2.c0 input gradients, 4 and 2 groups per CU) were 3 and 9 % slower
+// persistent (profiles/wino_persist_sites.txt) -- too few groups to pay for a
+// workgroup's claims, and nothing to balance.
+static size_t wino_persist_ctr_off(const IgemmArgs& a, int P) {
+  return ((size_t)P * a.N * a.a.Cg * 4 + 255) / 256 * 256;
+}
+bool wino_persist_applies(const IgemmArgs& a, int P, long long G, long long T) {
+  if (!g_wino_persist || G < 1 || G > 0x7fffffffLL || T + 64 > 0x7fffffffLL) return false;
+  if (G > num_cus() && G <= 4ll * num_cus()) return false;
+  return a.wino_ws != nullptr && wino_persist_ctr_off(a, P) + kWinoPersistCtrs * sizeof(unsigned) <= a.wino_ws_bytes;
+}
+static unsigned wino_persist_grid(long long G) {
+  long long w = num_cus();
+  if (g_wino_persist_wgs > 0) w = g_wino_persist_wgs;
+  return (unsigned)std::max<long long>(1, std::min(w, G));
+}
 
 hipError_t launch_wino_fused64p(const IgemmArgs& a, hipStream_t s) {
   if (!wino_fused64p_applies(a)) return hipErrorInvalidValue;
@@ -1786,8 +1980,22 @@ hipError_t launch_wino_fused64p(const IgemmArgs& a, hipStream_t s) {
   const long long nw = (long long)a.N * g.Cg;
   const int NB = a.N / 64;
   const long long G = (T + 31) / 32 * NB;
-  hipLaunchKernelGGL(k_wino4f_w8, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, a.b, a.N, g.Cg, V);
-  hipLaunchKernelGGL(k_wino4f64p, dim3((unsigned)G), dim3(512), 0, s, g, (const float*)V, a.N, T, Th, Tw, NB, a.e);
+  const bool persist = wino_persist_applies(a, 36, G, T);
+  const unsigned pgrid = persist ? wino_persist_grid(G) : 0u;
+  unsigned* ctr = persist ? reinterpret_cast<unsigned*>(reinterpret_cast<char*>(a.wino_ws) + wino_persist_ctr_off(a, 36))
+                          : nullptr;
+  hipLaunchKernelGGL(k_wino4f_w8, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, a.b, a.N, g.Cg, V, ctr, pgrid);
+  const dim3 grid(persist ? pgrid : (unsigned)G);
+#define WF64P(P_, F_)                                                                                            \
+  hipLaunchKernelGGL((k_wino4f64p<P_, F_>), grid, dim3(512), 0, s, g, (const float*)V, a.N, T, Th, Tw, NB, a.e, \
+                     (unsigned)G, ctr)
+  if (persist) {
+    if (a.e.yref == nullptr) WF64P(true, true); else WF64P(true, false);
+    ++g_wino_persist_launches;
+  } else {
+    if (a.e.yref == nullptr) WF64P(false, true); else WF64P(false, false);
+  }
+#undef WF64P
   return hipGetLastError();
 }
 
@@ -1810,8 +2018,10 @@ hipError_t launch_wino_fused64p(const IgemmArgs& a, hipStream_t s) {
 //     lane (mi, mq) ends with all 16 points of channels 4 mq .. +3 of tile mi
 //     for each block: A^T M A and the epilogue from registers, 16-B stores.
 // ---------------------------------------------------------------------------
-__global__ void k_wino2f_w8(const float* __restrict__ b, int N, int Cg, float* __restrict__ v) {
+__global__ void k_wino2f_w8(const float* __restrict__ b, int N, int Cg, float* __restrict__ v, unsigned* ctr,
+                            unsigned pgrid) {
   const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (ctr && i < kWinoPersistCtrs) ctr[i] = wp_ctr_init(pgrid, (int)i);  // the persistent form's claim counters
   if (i >= (long long)N * Cg) return;
   const int n = (int)(i / Cg), c = (int)(i - (long long)n * Cg);
   float g[3][3];
@@ -1842,38 +2052,62 @@ __global__ void k_wino2f_w8(const float* __restrict__ b, int N, int Cg, float* _
 // epilogue overlap the other's MFMAs (tile 75 waits 45 % of its wave cycles,
 // profiles/r05_pmc_summary_fp32.txt); the input transform is then done per
 // 32 output columns -- cheap in F(2x2) (24 adds per patch).
-template <int NC>
+// PERSIST (NC 64): the persistent form (see wp_resolve).  The patches are
+// staged through registers, so the next group's load(0) is issued before the
+// output stage, behind the biases (loaded at the top of a group), and the
+// forward's output stage then waits for nothing.  FWD: as wf64_output.
+template <int NC, bool PERSIST, bool FWD>
 __global__ __launch_bounds__(512, NC == 32 ? 2 : 1) void k_wino2f64(Gather g, const float* __restrict__ V, int N,
-                                                                   long long T, int Th, int Tw, int NB, Epilogue e) {
+                                                                   long long T, int Th, int Tw, int NB, Epilogue e,
+                                                                   unsigned G, unsigned* __restrict__ ctr) {
   constexpr int TT = 64;      // tiles per workgroup
   constexpr int PU = TT * 8;  // U point plane
   constexpr int PV = NC * 8;  // V point plane
   constexpr int NJ = NC / 32;  // 16-column blocks per wave
   __shared__ __attribute__((aligned(16))) float lds[16 * PU + 16 * PV];
+  __shared__ int sclaim[3];  // PERSIST: as k_wino4f64p
   float* Us = lds;
   float* Vs = lds + 16 * PU;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  long long bid = blockIdx.x;
-  const long long G = gridDim.x;
-  if ((G & 7) == 0) bid = (bid & 7) * (G >> 3) + (bid >> 3);  // an XCD's workgroups share tiles
-  const int nb = (int)(bid % NB);
-  const long long t0 = (bid / NB) * TT;
-  const int n0 = nb * NC;
-
-  // ---- loader role: patch (tile lt, channel lc) ----
+  using TI = typename std::conditional<PERSIST, unsigned, long long>::type;
   const int lt = tid >> 3, lc = tid & 7;
-  const long long t = t0 + lt;
-  int img = 0, ty = 0, tx = 0;
-  if (t < T) {
-    tx = (int)(t % Tw);
-    const long long r = t / Tw;
-    ty = (int)(r % Th);
-    img = (int)(r / Th);
+
+  // ---- this workgroup's first group ----
+  TI t0;
+  int n0, grp;
+  const int xcd = blockIdx.x & 7;
+  unsigned kfire = 0;
+  if constexpr (PERSIST) {
+    unsigned lo, hi;
+    wp_stretch(G, xcd, lo, hi);
+    const unsigned k0 = blockIdx.x >> 3;
+    int gid;
+    if (k0 < hi - lo) {
+      gid = (int)(lo + k0);
+    } else {  // more workgroups than groups in this stretch
+      if (tid == 0) sclaim[0] = wp_resolve(ctr, G, xcd, k0);
+      __syncthreads();
+      gid = sclaim[0];
+      if (gid < 0) return;
+    }
+    gid = __builtin_amdgcn_readfirstlane(gid);
+    if (tid == 0) kfire = atomicAdd(ctr + xcd, 1u);
+    n0 = (int)((unsigned)gid % (unsigned)NB) * NC;
+    t0 = (unsigned)gid / (unsigned)NB * (unsigned)TT;
+    grp = (int)(wp_block_of(G, (unsigned)gid) % kStatGroups);
+  } else {
+    long long bid = blockIdx.x;
+    const long long Gd = gridDim.x;
+    if ((Gd & 7) == 0) bid = (bid & 7) * (Gd >> 3) + (bid >> 3);  // an XCD's workgroups share tiles
+    n0 = (int)(bid % NB) * NC;
+    t0 = (bid / NB) * TT;
+    grp = (int)(blockIdx.x % kStatGroups);
   }
-  // rows / columns of the 4x4 patch inside the gather's input grid (Hg+2, Wg+2)
-  const int vrows = t < T ? min(4, g.Hg + 2 - 2 * ty) : 0;
-  const int vcols = t < T ? min(4, g.Wg + 2 - 2 * tx) : 0;
-  const bool wfull = __all(vrows == 4 && vcols == 4);
+
+  // ---- loader role: patch (tile lt, channel lc): rows / columns of the 4x4
+  // patch inside the gather's input grid (Hg+2, Wg+2) ----
+  WfPatch pc = wf_patch<2, TI>(t0 + (TI)lt, (TI)T, Th, Tw, g.Hg, g.Wg);
+  bool wfull = __all(pc.vrows == 4 && pc.vcols == 4);
   float* const ubase = Us + lt * 8 + wf8_slot(lt, lc & 3) + (lc >> 2);
   float raw[16];
   float sc = 1.f, sh = 0.f;  // the chunk's producer BN+ReLU (loaded with raw)
@@ -1895,7 +2129,7 @@ __global__ __launch_bounds__(512, NC == 32 ? 2 : 1) void k_wino2f64(Gather g, co
       sh = (second ? g.s[1].shift : g.s[0].shift)[cl];
     }
     const char* sb = reinterpret_cast<const char*>(sp);
-    const unsigned o0 = ((unsigned)((img * sH + 2 * ty + soy) * sW + 2 * tx + sox) * sC + cl) * 4u;
+    const unsigned o0 = ((unsigned)((pc.img * sH + 2 * pc.ty + soy) * sW + 2 * pc.tx + sox) * sC + cl) * 4u;
     const unsigned rs = (unsigned)sW * sC * 4u, cs = (unsigned)sC * 4u;
     if (wfull) {
 #pragma unroll
@@ -1904,7 +2138,7 @@ __global__ __launch_bounds__(512, NC == 32 ? 2 : 1) void k_wino2f64(Gather g, co
         for (int xx = 0; xx < 4; ++xx)
           raw[yy * 4 + xx] = *reinterpret_cast<const float*>(sb + (o0 + (yy * rs + xx * cs)));
     } else {  // clamp to the last in-window row / column (zeroed in commit)
-      const unsigned lr = (unsigned)max(vrows - 1, 0), lcn = (unsigned)max(vcols - 1, 0);
+      const unsigned lr = (unsigned)max(pc.vrows - 1, 0), lcn = (unsigned)max(pc.vcols - 1, 0);
 #pragma unroll
       for (int yy = 0; yy < 4; ++yy)
 #pragma unroll
@@ -1919,9 +2153,9 @@ __global__ __launch_bounds__(512, NC == 32 ? 2 : 1) void k_wino2f64(Gather g, co
     __builtin_amdgcn_s_waitcnt(0x0F70);  // raw(kc), sc, sh: retired visibly before the DMAs queue
 #pragma unroll
     for (int j = 0; j < 2 * NJ; ++j) {
-      const int pc = wave + 8 * j;  // 1-KB piece: point pc / NJ, part pc % NJ
-      dma_sv((unsigned)((((size_t)kc * 16 + pc / NJ) * N + n0) * 32) + (unsigned)((pc % NJ) * 1024 + lane * 16),
-             vbase, vlds + (unsigned)((pc / NJ) * PV * 4 + (pc % NJ) * 1024));
+      const int pc2 = wave + 8 * j;  // 1-KB piece: point pc2 / NJ, part pc2 % NJ
+      dma_sv((unsigned)((((size_t)kc * 16 + pc2 / NJ) * N + n0) * 32) + (unsigned)((pc2 % NJ) * 1024 + lane * 16),
+             vbase, vlds + (unsigned)((pc2 / NJ) * PV * 4 + (pc2 % NJ) * 1024));
     }
     if (scp) {
 #pragma unroll
@@ -1929,7 +2163,7 @@ __global__ __launch_bounds__(512, NC == 32 ? 2 : 1) void k_wino2f64(Gather g, co
     }
     if (!wfull) {
 #pragma unroll
-      for (int q = 0; q < 16; ++q) raw[q] = (q / 4 < vrows && q % 4 < vcols) ? raw[q] : 0.f;
+      for (int q = 0; q < 16; ++q) raw[q] = (q / 4 < pc.vrows && q % 4 < pc.vcols) ? raw[q] : 0.f;
     }
     // B^T d (rows), then (.) B (columns): k_wino_in's transform
     float ev[4][4];
@@ -1955,124 +2189,153 @@ __global__ __launch_bounds__(512, NC == 32 ? 2 : 1) void k_wino2f64(Gather g, co
   const int mi = lane & 15, mq = lane >> 4;
   const int aoff = (16 * th + mi) * 8 + wf8_slot(16 * th + mi, mq);
   const int boff = (16 * NJ * ch + mi) * 8 + wf8_slot(mi, mq);  // rows 16 (NJ ch + j) + mi and mi agree on bits 2-3
-  floatx4 acc[16][NJ];
-#pragma unroll
-  for (int p = 0; p < 16; ++p)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[p][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
-  load(0);
-  for (int kc = 0; kc < nk; ++kc) {
-    commit(kc);
-    __syncthreads();
-    if (kc + 1 < nk) load(kc + 1);
-#pragma unroll
-    for (int p = 0; p < 16; ++p) {
-      const float2 a = *reinterpret_cast<const float2*>(Us + p * PU + aoff);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const float2 b = *reinterpret_cast<const float2*>(Vs + p * PV + boff + 16 * j * 8);
-        acc[p][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.x, a.x, acc[p][j], 0, 0, 0);
-        acc[p][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.y, a.y, acc[p][j], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-
-  // ---- output: tile 16 th + mi, channels n0 + 16 (NJ ch + j) + 4 mq + (0..3) ----
-  const long long tt = t0 + 16 * th + mi;
   const bool want = e.stats || e.yref || e.colsum1;
   const int nsplit = e.n_split < N ? e.n_split : N;
-  const int grp = blockIdx.x % kStatGroups;
+  load(0);
+  if constexpr (PERSIST) {
+    if (tid == 0) sclaim[1] = wp_resolve(ctr, G, xcd, kfire);  // read behind the chunk loop's barriers
+  }
+  for (int it = 0;; ++it) {
+    floatx4 acc[16][NJ];
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int col0 = n0 + 16 * NJ * ch + 16 * j + 4 * mq;
-    const bool second = col0 >= e.n_split;  // uniform per 16-channel block (n_split % 16 == 0)
-    float* dptr = second ? e.d[1].ptr : e.d[0].ptr;
-    const int dC = second ? e.d[1].C : e.d[0].C;
-    const int dcol = second ? col0 - e.n_split : col0;
-    const bool bwd_mask = e.yref != nullptr && !second;
-    const float4 bias = e.bias ? ld4(e.bias + col0) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 bsc = make_float4(0.f, 0.f, 0.f, 0.f), bsh = bsc, bmu = bsc, bis = bsc;
-    if (bwd_mask) { bsc = ld4(e.bn_scale + col0); bsh = ld4(e.bn_shift + col0); bmu = ld4(e.bn_mean + col0); bis = ld4(e.bn_invstd + col0); }
-    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-    if (tt < T) {
-      const int ox = (int)(tt % Tw);
-      const long long rq = tt / Tw;
-      const int oy = (int)(rq % Th), on = (int)(rq / Th);
-      float4 y4[4];  // mask operands first, one wait (k_wino4f64)
-      if (bwd_mask) {
+    for (int p = 0; p < 16; ++p)
 #pragma unroll
-        for (int a = 0; a < 2; ++a)
+      for (int j = 0; j < NJ; ++j) acc[p][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+    float4 biasv[NJ];  // PERSIST: loaded ahead of the next group's patches
+    if constexpr (PERSIST) {
 #pragma unroll
-          for (int bb = 0; bb < 2; ++bb) {
-            const int y = min(2 * oy + a, g.Hg - 1), x = min(2 * ox + bb, g.Wg - 1);
-            y4[a * 2 + bb] = ld4(e.yref + ((size_t)(on * g.Hg + y) * g.Wg + x) * dC + dcol);
-          }
-      }
-      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) once: see k_wino4f64's epilogue
-      float o[4][2][2];  // [channel][row][col] = A^T M A
+      for (int j = 0; j < NJ; ++j)
+        biasv[j] = e.bias ? ld4(e.bias + n0 + 16 * NJ * ch + 16 * j + 4 * mq) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (int kc = 0; kc < nk; ++kc) {
+      commit(kc);
+      __syncthreads();
+      if (kc + 1 < nk) load(kc + 1);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float w[2][4];
+      for (int p = 0; p < 16; ++p) {
+        const float2 a = *reinterpret_cast<const float2*>(Us + p * PU + aoff);
 #pragma unroll
-        for (int xx = 0; xx < 4; ++xx) {
-          const float m0 = acc[0 * 4 + xx][j][r], m1 = acc[1 * 4 + xx][j][r];
-          const float m2 = acc[2 * 4 + xx][j][r], m3 = acc[3 * 4 + xx][j][r];
-          w[0][xx] = m0 + m1 + m2;
-          w[1][xx] = m1 - m2 - m3;
+        for (int j = 0; j < NJ; ++j) {
+          const float2 b = *reinterpret_cast<const float2*>(Vs + p * PV + boff + 16 * j * 8);
+          acc[p][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.x, a.x, acc[p][j], 0, 0, 0);
+          acc[p][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.y, a.y, acc[p][j], 0, 0, 0);
         }
+      }
+      __syncthreads();
+    }
+
+    // ---- output: tile 16 th + mi, channels n0 + 16 (NJ ch + j) + 4 mq + (0..3) ----
+    const TI tt = t0 + (TI)(16 * th + mi);
+    const int on0 = n0, ogrp = grp;
+    int gnext = -1;
+    if constexpr (PERSIST) {  // the next group's first patches, in flight over the output stage
+      gnext = __builtin_amdgcn_readfirstlane(sclaim[1 + (it & 1)]);
+      if (gnext >= 0) {
+        n0 = (int)((unsigned)gnext % (unsigned)NB) * NC;
+        t0 = (unsigned)gnext / (unsigned)NB * (unsigned)TT;
+        grp = (int)(wp_block_of(G, (unsigned)gnext) % kStatGroups);
+        pc = wf_patch<2, TI>(t0 + (TI)lt, (TI)T, Th, Tw, g.Hg, g.Wg);
+        wfull = __all(pc.vrows == 4 && pc.vcols == 4);
+        load(0);
+        if (tid == 0) kfire = atomicAdd(ctr + xcd, 1u);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int col0 = on0 + 16 * NJ * ch + 16 * j + 4 * mq;
+      const bool second = col0 >= e.n_split;  // uniform per 16-channel block (n_split % 16 == 0)
+      float* dptr = second ? e.d[1].ptr : e.d[0].ptr;
+      const int dC = second ? e.d[1].C : e.d[0].C;
+      const int dcol = second ? col0 - e.n_split : col0;
+      const bool bwd_mask = !FWD && e.yref != nullptr && !second;
+      float4 bias;
+      if constexpr (PERSIST) bias = biasv[j];
+      else bias = e.bias ? ld4(e.bias + col0) : make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 bsc = make_float4(0.f, 0.f, 0.f, 0.f), bsh = bsc, bmu = bsc, bis = bsc;
+      if (bwd_mask) { bsc = ld4(e.bn_scale + col0); bsh = ld4(e.bn_shift + col0); bmu = ld4(e.bn_mean + col0); bis = ld4(e.bn_invstd + col0); }
+      float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+      if (tt < (TI)T) {
+        const int ox = (int)(tt % (TI)Tw);
+        const TI rq = tt / (TI)Tw;
+        const int oy = (int)(rq % (TI)Th), on = (int)(rq / (TI)Th);
+        float4 y4[4];  // mask operands first, one wait (k_wino4f64)
+        if (bwd_mask) {
+#pragma unroll
+          for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb) {
+              const int y = min(2 * oy + a, g.Hg - 1), x = min(2 * ox + bb, g.Wg - 1);
+              y4[a * 2 + bb] = ld4(e.yref + ((size_t)(on * g.Hg + y) * g.Wg + x) * dC + dcol);
+            }
+        }
+        // vmcnt(0) once: see k_wino4f64's epilogue (not where it would only wait for the prefetched patches)
+        if constexpr (!(PERSIST && FWD)) __builtin_amdgcn_s_waitcnt(0x0F70);
+        float o[4][2][2];  // [channel][row][col] = A^T M A
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float w[2][4];
+#pragma unroll
+          for (int xx = 0; xx < 4; ++xx) {
+            const float m0 = acc[0 * 4 + xx][j][r], m1 = acc[1 * 4 + xx][j][r];
+            const float m2 = acc[2 * 4 + xx][j][r], m3 = acc[3 * 4 + xx][j][r];
+            w[0][xx] = m0 + m1 + m2;
+            w[1][xx] = m1 - m2 - m3;
+          }
+#pragma unroll
+          for (int a = 0; a < 2; ++a) {
+            o[r][a][0] = w[a][0] + w[a][1] + w[a][2];
+            o[r][a][1] = w[a][1] - w[a][2] - w[a][3];
+          }
+        }
+        const float bsv[4] = {bias.x, bias.y, bias.z, bias.w};
+        const float scv[4] = {bsc.x, bsc.y, bsc.z, bsc.w}, shv[4] = {bsh.x, bsh.y, bsh.z, bsh.w};
+        const float muv[4] = {bmu.x, bmu.y, bmu.z, bmu.w}, isv[4] = {bis.x, bis.y, bis.z, bis.w};
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
-          o[r][a][0] = w[a][0] + w[a][1] + w[a][2];
-          o[r][a][1] = w[a][1] - w[a][2] - w[a][3];
-        }
-      }
-      const float bsv[4] = {bias.x, bias.y, bias.z, bias.w};
-      const float scv[4] = {bsc.x, bsc.y, bsc.z, bsc.w}, shv[4] = {bsh.x, bsh.y, bsh.z, bsh.w};
-      const float muv[4] = {bmu.x, bmu.y, bmu.z, bmu.w}, isv[4] = {bis.x, bis.y, bis.z, bis.w};
+          const int y = 2 * oy + a;
+          if (y >= g.Hg) continue;
 #pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        const int y = 2 * oy + a;
-        if (y >= g.Hg) continue;
+          for (int bb = 0; bb < 2; ++bb) {
+            const int x = 2 * ox + bb;
+            if (x >= g.Wg) continue;
+            const size_t idx = ((size_t)(on * g.Hg + y) * g.Wg + x) * dC + dcol;
+            const float4 yq = bwd_mask ? y4[a * 2 + bb] : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float yv[4] = {yq.x, yq.y, yq.z, yq.w};
+            float v[4];
 #pragma unroll
-        for (int bb = 0; bb < 2; ++bb) {
-          const int x = 2 * ox + bb;
-          if (x >= g.Wg) continue;
-          const size_t idx = ((size_t)(on * g.Hg + y) * g.Wg + x) * dC + dcol;
-          const float4 yq = bwd_mask ? y4[a * 2 + bb] : make_float4(0.f, 0.f, 0.f, 0.f);
-          const float yv[4] = {yq.x, yq.y, yq.z, yq.w};
-          float v[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = wf_epi(o[r][a][bb] + bsv[r], yv[r], scv[r], shv[r], muv[r], isv[r],
-                                                     bwd_mask, e.relu, s1[r], s2[r]);
-          st4(dptr + idx, make_float4(v[0], v[1], v[2], v[3]));
-        }
-      }
-    }
-    if (!want) continue;
-    // the 16 lanes of a quarter hold the same 4 channels (other tiles)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int o2 = 1; o2 < 16; o2 <<= 1) {
-        s1[r] += __shfl_xor(s1[r], o2);
-        s2[r] += __shfl_xor(s2[r], o2);
-      }
-    if (mi == 0) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int col = col0 + r;
-        if (col < nsplit) {
-          double* st = e.yref ? e.bstats : e.stats;
-          if (st) {
-            atomicAdd(st + ((size_t)grp * nsplit + col) * 2 + 0, (double)s1[r]);
-            atomicAdd(st + ((size_t)grp * nsplit + col) * 2 + 1, (double)s2[r]);
+            for (int r = 0; r < 4; ++r) v[r] = wf_epi(o[r][a][bb] + bsv[r], yv[r], scv[r], shv[r], muv[r], isv[r],
+                                                       bwd_mask, e.relu, s1[r], s2[r]);
+            st4(dptr + idx, make_float4(v[0], v[1], v[2], v[3]));
           }
-        } else if (e.colsum1) {
-          atomicAdd(e.colsum1 + (size_t)grp * (N - nsplit) + (col - nsplit), (double)s1[r]);
+        }
+      }
+      if (!want) continue;
+      // the 16 lanes of a quarter hold the same 4 channels (other tiles)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int o2 = 1; o2 < 16; o2 <<= 1) {
+          s1[r] += __shfl_xor(s1[r], o2);
+          s2[r] += __shfl_xor(s2[r], o2);
+        }
+      if (mi == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int col = col0 + r;
+          if (col < nsplit) {
+            double* st = e.yref ? e.bstats : e.stats;
+            if (st) {
+              atomicAdd(st + ((size_t)ogrp * nsplit + col) * 2 + 0, (double)s1[r]);
+              atomicAdd(st + ((size_t)ogrp * nsplit + col) * 2 + 1, (double)s2[r]);
+            }
+          } else if (e.colsum1) {
+            atomicAdd(e.colsum1 + (size_t)ogrp * (N - nsplit) + (col - nsplit), (double)s1[r]);
+          }
         }
       }
     }
+    if (!PERSIST || gnext < 0) break;
+    if (tid == 0) sclaim[1 + ((it + 1) & 1)] = wp_resolve(ctr, G, xcd, kfire);
   }
 }
 
@@ -2101,11 +2364,25 @@ hipError_t launch_wino_fused2(const IgemmArgs& a, hipStream_t s, int nc) {
   const long long nw = (long long)a.N * g.Cg;
   const int NB = a.N / nc;
   const long long G = (T + 63) / 64 * NB;
-  hipLaunchKernelGGL(k_wino2f_w8, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, a.b, a.N, g.Cg, V);
-  if (nc == 64)
-    hipLaunchKernelGGL(k_wino2f64<64>, dim3((unsigned)G), dim3(512), 0, s, g, (const float*)V, a.N, T, Th, Tw, NB, a.e);
-  else
-    hipLaunchKernelGGL(k_wino2f64<32>, dim3((unsigned)G), dim3(512), 0, s, g, (const float*)V, a.N, T, Th, Tw, NB, a.e);
+  const bool persist = nc == 64 && wino_persist_applies(a, 16, G, T);  // tile 75 (tile 77 keeps two workgroups per CU)
+  const unsigned pgrid = persist ? wino_persist_grid(G) : 0u;
+  unsigned* ctr = persist ? reinterpret_cast<unsigned*>(reinterpret_cast<char*>(a.wino_ws) + wino_persist_ctr_off(a, 16))
+                          : nullptr;
+  hipLaunchKernelGGL(k_wino2f_w8, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, a.b, a.N, g.Cg, V, ctr, pgrid);
+  const dim3 grid(persist ? pgrid : (unsigned)G);
+  const bool fwd = a.e.yref == nullptr;
+#define WF2(NC_, P_, F_)                                                                                            \
+  hipLaunchKernelGGL((k_wino2f64<NC_, P_, F_>), grid, dim3(512), 0, s, g, (const float*)V, a.N, T, Th, Tw, NB, a.e, \
+                     (unsigned)G, ctr)
+  if (persist) {
+    if (fwd) WF2(64, true, true); else WF2(64, true, false);
+    ++g_wino_persist_launches;
+  } else if (nc == 64) {
+    if (fwd) WF2(64, false, true); else WF2(64, false, false);
+  } else {
+    if (fwd) WF2(32, false, true); else WF2(32, false, false);
+  }
+#undef WF2
   return hipGetLastError();
 }
 

@@ -117,6 +117,7 @@ SIGNATURES = {
     "unet_fused_bnb_sites": (ctypes.c_longlong, [_i]),
     "unet_wgrad_oihw_sites": (ctypes.c_longlong, [_i]),
     "unet_igemm_plane_launches": (ctypes.c_longlong, [_i]),
+    "unet_wino_persist_launches": (ctypes.c_longlong, [_i]),
     "unet_tuning_save": (_i, [ctypes.c_char_p]),
     "unet_tuning_load": (_i, [ctypes.c_char_p]),
 }
