@@ -290,6 +290,70 @@ def relu_bwd(dy, y):
     return dy * (y > 0)
 
 
+def bn_eval_bwd(dz, x, gamma, rm, rv, eps=BN_EPS):
+    """Autograd of bn_eval_fwd: the running statistics are constants, so
+    dx = gamma * invstd * dz, dgamma = sum dz * xhat, dbeta = sum dz."""
+    C = dz.shape[-1]
+    invstd = 1.0 / np.sqrt(rv + eps)
+    xhat = (x - rm) * invstd
+    return gamma * invstd * dz, (dz * xhat).reshape(-1, C).sum(0), dz.reshape(-1, C).sum(0)
+
+
+def bn_relu_fwd(x, gamma, beta, rm, rv, training=True, relu=True, momentum=BN_MOMENTUM, eps=BN_EPS):
+    """nn.BatchNorm2d followed by nn.ReLU when relu (models/unet_model.py:12-13),
+    any eps / momentum.  Training: batch statistics, running buffers updated
+    (rm / rv None = track_running_stats off); eval: the running statistics.
+    Returns y, cache (for bn_relu_bwd), the statistics used (mean, invstd) and
+    the running buffers after the call."""
+    if training:
+        z, (xhat, invstd), mean, var_unb = bn_train_fwd(x, gamma, beta, eps)
+        if rm is not None:
+            rm, rv = bn_update_running(rm, rv, mean, var_unb, momentum)
+    else:
+        z = bn_eval_fwd(x, gamma, beta, rm, rv, eps)
+        mean, invstd = rm, 1.0 / np.sqrt(rv + eps)
+        xhat = (x - mean) * invstd
+    y = relu_fwd(z) if relu else z
+    return y, (xhat, invstd), mean, invstd, rm, rv
+
+
+def bn_relu_bwd(dy, y, cache, gamma, training=True, relu=True):
+    """Autograd of bn_relu_fwd: (dx, dgamma, dbeta); y is the forward's output
+    (the ReLU mask)."""
+    dz = relu_bwd(dy, y) if relu else dy
+    if training:
+        return bn_train_bwd(dz, cache, gamma)
+    xhat, invstd = cache
+    C = dz.shape[-1]
+    return gamma * invstd * dz, (dz * xhat).reshape(-1, C).sum(0), dz.reshape(-1, C).sum(0)
+
+
+def conv_first_fwd(x_nchw, w, b):
+    """The first conv (models/unet_model.py:11 of inc) from the NCHW network
+    input: y NHWC (N,H-2,W-2,Co)."""
+    return conv_valid_fwd(np.ascontiguousarray(x_nchw.transpose(0, 2, 3, 1)), w, b)
+
+
+def conv_first_bwd(x_nchw, w, dy, need_dx=True):
+    """Autograd of conv_first_fwd: (dx NCHW or None, dw OIHW, db)."""
+    dx, dw, db = conv_valid_bwd(np.ascontiguousarray(x_nchw.transpose(0, 2, 3, 1)), w, dy, need_dx)
+    return (np.ascontiguousarray(dx.transpose(0, 3, 1, 2)) if need_dx else None), dw, db
+
+
+def conv1x1_fwd(x, w, b):
+    """OutConv's nn.Conv2d(C, K, kernel_size=1) (models/unet_model.py:60):
+    x (N,H,W,C) NHWC, w (K,C), b (K,) -> logits NCHW (N,K,H,W)."""
+    return np.ascontiguousarray((x @ w.astype(x.dtype).T + b.astype(x.dtype)).transpose(0, 3, 1, 2))
+
+
+def conv1x1_bwd(x, w, dlogits_nchw):
+    """Autograd of conv1x1_fwd: dx (N,H,W,C), dw (K,C), db (K,)."""
+    K, C = w.shape
+    d = np.ascontiguousarray(dlogits_nchw.transpose(0, 2, 3, 1))
+    df = d.reshape(-1, K)
+    return d @ w.astype(d.dtype), df.T @ x.reshape(-1, C), df.sum(0)
+
+
 def maxpool2_fwd(x):
     """nn.MaxPool2d(2) (models/unet_model.py:28): 2x2 stride 2, floor mode.
 

@@ -1895,14 +1895,35 @@ hipError_t launch_iou(const uint8_t* a, const uint8_t* b, size_t n, unsigned lon
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_channel_stats(const float* __restrict__ x, long long pixels, int C,
                                                        double* __restrict__ st) {
+  // fp64 partials (the squares are exact): the finalize forms the variance as
+  // E[x^2] - mean^2, which cancels where a channel's spread is small against
+  // its mean; fp32 partials left invstd 6e-5 off on a 3-pixel batch
   const int C4 = C / 4, tid = threadIdx.x, cg = tid % C4, ppb = 256 / C4;
-  float sa[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0};
+  double sa[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0};
   for (long long p = (long long)blockIdx.x * ppb + tid / C4; p < pixels; p += (long long)gridDim.x * ppb) {
     const float4 v = ld4(x + p * C + cg * 4);
-    sa[0] += v.x; sa[1] += v.y; sa[2] += v.z; sa[3] += v.w;
-    sb[0] += v.x * v.x; sb[1] += v.y * v.y; sb[2] += v.z * v.z; sb[3] += v.w * v.w;
+    const double vx = v.x, vy = v.y, vz = v.z, vw = v.w;
+    sa[0] += vx; sa[1] += vy; sa[2] += vz; sa[3] += vw;
+    sb[0] += vx * vx; sb[1] += vy * vy; sb[2] += vz * vz; sb[3] += vw * vw;
   }
-  reduce_pairs_to_global(sa, sb, C4, C, st + (size_t)(blockIdx.x % kStatGroups) * C * 2);
+  // as reduce_pairs_to_global, in fp64
+  __shared__ double red[256][9];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { red[tid][k] = sa[k]; red[tid][4 + k] = sb[k]; }
+  __syncthreads();
+  if (tid < C4) {
+    double ta[4] = {0, 0, 0, 0}, tb[4] = {0, 0, 0, 0};
+    for (int r = tid; r < 256; r += C4) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { ta[k] += red[r][k]; tb[k] += red[r][4 + k]; }
+    }
+    double* dst = st + (size_t)(blockIdx.x % kStatGroups) * C * 2;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      atomicAdd(dst + (size_t)(tid * 4 + k) * 2 + 0, ta[k]);
+      atomicAdd(dst + (size_t)(tid * 4 + k) * 2 + 1, tb[k]);
+    }
+  }
 }
 __global__ __launch_bounds__(256) void k_bn_bwd_stats(const float* __restrict__ dy, const float* __restrict__ x,
                                                       const float* mean, const float* invstd, long long pixels,
