@@ -456,6 +456,47 @@ int unet_warping_error(const uint16_t* gt, const uint8_t* pred, int n, int h, in
                        int max_sweeps, int flags, uint8_t* warped, int64_t* counts, void* ws, unet_stream_t stream);
 void unet_simple_point_table(uint8_t out[256]);
 
+/* Marker-seeded instance masks: unet_instance_masks with touching cells split
+ * (the reference's README leaves "instance separation" to a post-processing
+ * it does not have).  mask (n, h, w) uint8 on the device; all numbering is
+ * per frame.
+ *   fg = mask > 0.
+ *   d2(p): exact squared Euclidean distance from foreground pixel p to the
+ *     nearest background pixel inside the frame (outside the frame is not
+ *     background: scipy.ndimage.distance_transform_edt); 0 on background;
+ *     2^30 everywhere in a frame without a background pixel.
+ *   Marker set: markers == NULL: fg & (d2 >= core_d2), 0 <= core_d2 <= 2^30;
+ *     else (markers > 0) & fg (core_d2 is then ignored, d2 computed only if
+ *     asked for).  Marker labels: its 8-connected components, numbered 1, 2,
+ *     ... in raster order of their first pixel.
+ *   Growth: with keys (dist, label) in lexicographic order, (0, label) on
+ *     markers, the least fixed point of key(p) = min(key(p), key(q) + (1, 0))
+ *     over the foreground 8-neighbours q of foreground p: every foreground
+ *     pixel connected to a marker takes the label of the marker at the
+ *     smallest 8-connected geodesic distance within fg, the smallest label
+ *     among equals.  A foreground component without a marker stays one
+ *     segment.
+ *   labels (uint16): the segments numbered 1, 2, ... in raster order of their
+ *     first pixel; those under min_size pixels set to 0 without renumbering.
+ *   d2 (may be NULL): (n, h, w) int32.
+ *   info (n x 4 int32): markers, segments before the min_size cut, the largest
+ *     geodesic distance assigned, overflow (non-zero when markers or segments
+ *     exceed 65535; the frame's labels are then unspecified).  The keys are
+ *     64-bit (distance and label 32 bits each), so the distance cannot
+ *     saturate.
+ * With core_d2 == 0 the labels equal unet_instance_masks's.  One workgroup per
+ * frame grows the labels by in-place directional sweeps (down, up, right,
+ * left) until one round changes nothing, in one launch; the fixed point is
+ * unique, so the result does not depend on the schedule
+ * (unet_set_tuning("split_threads", t) sets the workgroup's size).  No host
+ * synchronisation.  ws >= unet_split_instances_ws_bytes(n, h, w), 256-byte
+ * aligned.  -EINVAL before any launch (and a workspace size of 0) for n, h or
+ * w < 1, h or w > 16384, n > 65535, n h w >= 2^31, core_d2 outside [0, 2^30]
+ * (markers == NULL), min_size < 0, a null mask / labels / info / ws. */
+size_t unet_split_instances_ws_bytes(int n, int h, int w);
+int unet_split_instances(const uint8_t* mask, const uint8_t* markers, int n, int h, int w, int core_d2, int min_size,
+                         uint16_t* labels, int32_t* d2, int32_t* info, void* ws, unet_stream_t stream);
+
 /* Tuning hooks, process-global:
  *  "autotune"      1 (default, or env UNET_AUTOTUNE) = the plan times the
  *                  applicable GEMM variants (tile shape, split-K, wgrad pixel
@@ -548,7 +589,10 @@ void unet_simple_point_table(uint8_t out[256]);
  *                  the default, 32); unet_ctc_ws_bytes reads it.
  *  "ctc_dense_cells" largest (n_gt + 1)(n_res + 1) that unet_ctc_add_frames
  *                  counts in a dense LDS table (0..8192, 0 = every frame by
- *                  hash; -1 = the default, 4096). */
+ *                  hash; -1 = the default, 4096).
+ *  "split_threads" t (tests; 64..1024, a multiple of 64; -1 = the default,
+ *                  1024): threads of unet_split_instances's growth workgroup
+ *                  (same bits for every value). */
 int unet_set_tuning(const char* key, int value);
 /* Text report of the tuned GEMM choices (one line per shape: key, heuristic
  * time, chosen variant and time).  Copies up to len-1 bytes + NUL into buf

@@ -273,6 +273,20 @@ static void test_warp() {
   CHECK(unet_warping_error(nullptr, p, 1, 2, 2, 4, 1, 0, 0, nullptr, c5, nullptr, nullptr) == -EINVAL);
   CHECK(unet_warping_error(g, p, 1, 2, 2, 4, 1, 0, UNET_WARP_FORCE_WS, nullptr, c5, nullptr, nullptr) == -EINVAL);  // no workspace
   CHECK(std::strstr(unet_last_error(), "unet_warping_error") != nullptr);
+  // marker-seeded instance masks: rejected before any launch
+  CHECK(unet_split_instances_ws_bytes(0, 4, 4) == 0 && unet_split_instances_ws_bytes(1, 16385, 4) == 0 &&
+        unet_split_instances_ws_bytes(1, 4, 16385) == 0 && unet_split_instances_ws_bytes(65536, 1, 1) == 0 &&
+        unet_split_instances_ws_bytes(8, 16384, 16384) == 0);
+  uint16_t lab[4];
+  int32_t info[4];
+  CHECK(unet_split_instances(p, nullptr, 0, 2, 2, 4, 1, lab, nullptr, info, nullptr, nullptr) == -EINVAL);
+  CHECK(unet_split_instances(p, nullptr, 1, 2, 2, -1, 1, lab, nullptr, info, nullptr, nullptr) == -EINVAL);
+  CHECK(unet_split_instances(p, nullptr, 1, 2, 2, (1 << 30) + 1, 1, lab, nullptr, info, nullptr, nullptr) == -EINVAL);
+  CHECK(unet_split_instances(p, nullptr, 1, 2, 2, 4, -1, lab, nullptr, info, nullptr, nullptr) == -EINVAL);
+  CHECK(unet_split_instances(p, nullptr, 1, 2, 2, 4, 1, lab, nullptr, info, nullptr, nullptr) == -EINVAL);  // no workspace
+  CHECK(std::strstr(unet_last_error(), "unet_split_instances") != nullptr);
+  CHECK(unet_set_tuning("split_threads", 96) == -EINVAL && unet_set_tuning("split_threads", 128) == 0 &&
+        unet_set_tuning("split_threads", -1) == 0);
 }
 
 static void test_misc() {

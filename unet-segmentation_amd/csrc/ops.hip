@@ -605,6 +605,10 @@ int unet_set_tuning(const char* key, int value) {
     if (value < -1 || (value == 0 && k == "ctc_chunk_frames")) return -EINVAL;  // -1 = the default
     (k == "ctc_chunk_frames" ? g_ctc_chunk_frames : g_ctc_dense_cells) = value;
   }
+  else if (k == "split_threads") {  // split.hip: the growth workgroup's size, -1 = the default
+    if (value != -1 && (value < 64 || value > 1024 || value % 64)) return -EINVAL;
+    g_split_threads = value;
+  }
   else if (k == "deterministic") g_deterministic = value != 0;  // 0: bf16 plans pool with the 4-channel kernel (A/B tests)
   else if (k == "op_precision") {
     if (value != UNET_PREC_FP32 && value != UNET_PREC_BF16 && value != UNET_PREC_BF16X3) return -EINVAL;

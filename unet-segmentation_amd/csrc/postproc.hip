@@ -24,31 +24,7 @@
 namespace unet {
 
 // ------------------------------- components ---------------------------------
-__device__ __forceinline__ int uf_find(const int* parent, int x) {
-  int p = parent[x];
-  while (p != x) {
-    x = p;
-    p = parent[x];
-  }
-  return x;
-}
-
-__device__ __forceinline__ void uf_union(int* parent, int a, int b) {
-  while (true) {
-    a = uf_find(parent, a);
-    b = uf_find(parent, b);
-    if (a == b) return;
-    if (a > b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = atomicMin(parent + b, a);
-    if (old == b) return;  // b was a root: now it points to a
-    b = old;
-  }
-}
-
+// uf_find / uf_union: unet_internal.h (shared with split.hip)
 // parent[i] = i for foreground, -1 for background (per image, global index)
 __global__ void k_cc_init(const uint8_t* __restrict__ m, size_t total, int* __restrict__ parent) {
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -97,12 +73,32 @@ __global__ void k_cc_label(size_t total, size_t hw, const int* __restrict__ pare
   out[i] = (int)size[r] < min_size ? 0 : (uint16_t)id;
 }
 
-size_t instance_masks_ws_bytes(int n, int h, int w) {
-  const size_t total = (size_t)n * h * w;
+size_t cc_scan_bytes(size_t total) {
   size_t scan = 0;
   if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan, (const int*)nullptr, (int*)nullptr, (int)total) != hipSuccess)
-    return 0;  // the launch then fails on the missing workspace
-  return 4 * (total * 4 + 256) + scan + 256;
+    return 0;
+  return scan;
+}
+
+void cc_union_mask(const uint8_t* m, int n, int h, int w, int* parent, hipStream_t s) {
+  const size_t total = (size_t)n * h * w;
+  const unsigned g = (unsigned)((total + 255) / 256);
+  hipLaunchKernelGGL(k_cc_init, dim3(g), dim3(256), 0, s, m, total, parent);
+  hipLaunchKernelGGL(k_cc_union, dim3(g), dim3(256), 0, s, m, n, h, w, parent);
+}
+
+hipError_t cc_number(size_t total, int* parent, int* is_root, int* rank, unsigned* size, void* tmp, size_t scan,
+                     hipStream_t s) {
+  const hipError_t e = hipMemsetAsync(size, 0, total * 4, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_cc_flatten, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, total, parent, is_root, size);
+  return hipcub::DeviceScan::ExclusiveSum(tmp, scan, is_root, rank, (int)total, s);
+}
+
+size_t instance_masks_ws_bytes(int n, int h, int w) {
+  const size_t total = (size_t)n * h * w;
+  const size_t scan = cc_scan_bytes(total);  // 0: the launch then fails on the missing workspace
+  return scan ? 4 * (total * 4 + 256) + scan + 256 : 0;
 }
 
 static char* carve(char*& p, size_t bytes) {
@@ -124,15 +120,11 @@ hipError_t launch_instance_masks(const uint8_t* mask, int n, int h, int w, int m
   hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan, is_root, rank, (int)total, s);
   if (e != hipSuccess) return e;
   void* tmp = carve(p, scan);
-  const unsigned g = (unsigned)((total + 255) / 256);
-  e = hipMemsetAsync(size, 0, total * 4, s);
+  cc_union_mask(mask, n, h, w, parent, s);
+  e = cc_number(total, parent, is_root, rank, size, tmp, scan, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_cc_init, dim3(g), dim3(256), 0, s, mask, total, parent);
-  hipLaunchKernelGGL(k_cc_union, dim3(g), dim3(256), 0, s, mask, n, h, w, parent);
-  hipLaunchKernelGGL(k_cc_flatten, dim3(g), dim3(256), 0, s, total, parent, is_root, size);
-  e = hipcub::DeviceScan::ExclusiveSum(tmp, scan, is_root, rank, (int)total, s);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_cc_label, dim3(g), dim3(256), 0, s, total, (size_t)h * w, parent, rank, size, min_size, out);
+  hipLaunchKernelGGL(k_cc_label, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, total, (size_t)h * w, parent,
+                     rank, size, min_size, out);
   return hipGetLastError();
 }
 

@@ -382,9 +382,49 @@ hipError_t launch_tile_scatter(const float* lt, int k, int to, int nx, int first
 size_t instance_masks_ws_bytes(int n, int h, int w);
 hipError_t launch_instance_masks(const uint8_t* mask, int n, int h, int w, int min_size, uint16_t* out, void* ws,
                                  hipStream_t s);
+// The union-find labelling launch_instance_masks and split.hip share.  Roots are
+// a component's smallest linear index (its first pixel in raster order).
+__device__ __forceinline__ int uf_find(const int* parent, int x) {
+  int p = parent[x];
+  while (p != x) {
+    x = p;
+    p = parent[x];
+  }
+  return x;
+}
+
+__device__ __forceinline__ void uf_union(int* parent, int a, int b) {
+  while (true) {
+    a = uf_find(parent, a);
+    b = uf_find(parent, b);
+    if (a == b) return;
+    if (a > b) {
+      const int t = a;
+      a = b;
+      b = t;
+    }
+    const int old = atomicMin(parent + b, a);
+    if (old == b) return;  // b was a root: now it points to a
+    b = old;
+  }
+}
+
+// parent = the union-find forest of the 8-connected components of m != 0 (-1 on background)
+void cc_union_mask(const uint8_t* m, int n, int h, int w, int* parent, hipStream_t s);
+// flattens parent to the roots; is_root, size (pixels, at the roots), rank = exclusive scan of is_root;
+// tmp >= cc_scan_bytes(total)
+size_t cc_scan_bytes(size_t total);  // 0: hipcub refused
+hipError_t cc_number(size_t total, int* parent, int* is_root, int* rank, unsigned* size, void* tmp, size_t scan,
+                     hipStream_t s);
 size_t rand_index_ws_bytes(int h, int w);
 hipError_t launch_rand_index(const uint16_t* g, const uint16_t* p, int h, int w, double* out, void* ws,
                              hipStream_t s);
+
+// marker-seeded instance masks (split.hip)
+extern int g_split_threads;  // threads of the growth kernel's workgroup (tests; -1 = 1024)
+size_t split_instances_ws_bytes(int n, int h, int w);  // 0 for rejected sizes
+hipError_t launch_split_instances(const uint8_t* mask, const uint8_t* markers, int n, int h, int w, int core_d2,
+                                  int min_size, uint16_t* labels, int32_t* d2, int32_t* info, void* ws, hipStream_t s);
 
 // the text unet_last_error() returns on the calling thread (plan.hip)
 void set_last_error(const std::string& s);

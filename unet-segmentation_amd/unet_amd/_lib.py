@@ -109,6 +109,8 @@ SIGNATURES = {
     "unet_warping_error_ws_bytes": (_sz, [_i, _i, _i]),
     "unet_warping_error": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "unet_simple_point_table": (None, [_vp]),
+    "unet_split_instances_ws_bytes": (_sz, [_i, _i, _i]),
+    "unet_split_instances": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "unet_set_tuning": (_i, [ctypes.c_char_p, _i]),
     "unet_tuning_report": (_sz, [ctypes.c_char_p, _sz]),
     "unet_tuning_reset": (_i, []),
@@ -178,7 +180,7 @@ def stream_of(device=None):
 _HASHED = ["igemm.hip", "igemm_bf16.hip", "conv3_dma.hip", "conv3_ring.hip", "winograd.hip", "elementwise.hip", "elastic.hip",
            "tiling.hip", "weightmap.hip", "postproc.hip", "track.hip", "ops.hip", "plan.hip", "wgrad3_ring.hip",
            "conv3_ring_pt.hip", "peak.hip", "gemm_ring.hip", "wgradT_ring.hip", "conv3_flat.hip", "conv3_c64.hip", "gemm_ring_p1.hip",
-           "gemm_ring_p2.hip", "wgrad_plane.hip", "igemm_plane.hip", "ctc.hip", "warp.hip", "unet_internal.h", "gemm_common.h", "ring_common.h", "conv3_ring_kernel.h",
+           "gemm_ring_p2.hip", "wgrad_plane.hip", "igemm_plane.hip", "ctc.hip", "warp.hip", "split.hip", "unet_internal.h", "gemm_common.h", "ring_common.h", "conv3_ring_kernel.h",
            os.path.join("..", "..", "include", "unet_hip.h")]
 
 
