@@ -311,7 +311,53 @@ int unet_rand_index(const uint16_t* gt, const uint16_t* pred, int h, int w, doub
  *     first frame).  Host only (no device work).
  *   unet_tracker_tracks: writes up to cap rows (label, start, end, parent) in
  *     the res_track.txt order (start frame, then label; end >= start);
- *     returns the track count.
+ *     returns the track count.  A root track's parent is -1 as the reference
+ *     writes it; the Cell Tracking Challenge's res_track.txt writes 0 there.
+ *   Frame maps: for every frame it was given (by either step function) the
+ *     tracker keeps the frame number, the frame's ascending object labels and,
+ *     per label, the id of the track that holds it when that frame's step ends
+ *     (active_tracks_by_obj_label[label] after the step; 0 = the object holds
+ *     no track).  A few bytes per object, kept for the tracker's life.
+ *     unet_tracker_num_frames: the number of maps.  unet_tracker_frame_map:
+ *     map `index` in the order the frames were given; writes the frame number
+ *     and up to cap (label, track id) pairs, returns the object count; any
+ *     output pointer may be NULL; -EINVAL for a bad index.  Host only.
+ *   unet_tracker_set_label_scope: UNET_TRACK_SCOPE_SHARED (default) keeps the
+ *     reference's single dictionary for the labels of the previous and the
+ *     current frame, with its quirk: a link "previous 3 -> current 4" followed
+ *     by "previous 4 -> current 5" takes the track from current object 4
+ *     again, which then holds none.  UNET_TRACK_SCOPE_FRAME reads and deletes
+ *     previous-frame labels in the table the previous step left and assigns
+ *     current-frame labels in a fresh one, which becomes "previous" when the
+ *     step ends; the step is otherwise the same.  -EBUSY once a frame was
+ *     given, -EINVAL for another value.
+ *   unet_tracker_relabel: labels and out (n, h, w) uint16 on the device (h, w
+ *     the tracker's), host_frames the n frame numbers.  out[i] = labels[i]
+ *     with every pixel replaced by the track id its label holds in the map of
+ *     frame host_frames[i] (the last one given under that number); background,
+ *     a label the map does not list and an object without a track give 0.
+ *     out == labels (in place) is allowed; any other overlap is not.  The
+ *     result is a Cell Tracking Challenge mask stack (mask%03d.tif).
+ *     One kernel launch for the whole stack: the tables of all n frames go
+ *     up in one copy, after which the stream is synchronised once (the host
+ *     staging buffer lives in the tracker and is rewritten by the next call),
+ *     then the launch; no per-frame launch or synchronisation.  The kernel
+ *     streams 16 bytes (8 pixels) per lane with scalar head and tail pixels
+ *     where a frame does not start on 16 bytes; each frame has one dense uint16
+ *     table of L entries, L = 1 + the highest label in the n maps rounded up
+ *     to 8, which a workgroup stages in LDS while L <= 8192 (16 KiB, so 8
+ *     workgroups of 256 lanes still share a CU's 160 KiB) and reads through L2
+ *     beyond.
+ *     ws >= unet_tracker_relabel_ws_bytes(n, h, w) bytes, 256-byte aligned:
+ *     n tables x 65,536 entries x 2 B (labels up to 65,535), rounded up to
+ *     256 B; 0 for n, h or w < 1.
+ *     Errors are returned before any device work, so before any pointer is
+ *     touched: -EINVAL (null or misaligned pointers, n < 0, a stack of more
+ *     than 2^31 - 1 workgroups of 8,192 pixels), -ENOENT (a frame number that was never given; unet_last_error()
+ *     names it), -ERANGE (one of the n maps holds a track id above 65,535,
+ *     which a 16-bit mask cannot carry); -EIO for a HIP error.  n = 0: 0.
+ *   unet_tracker_relabel_launches: relabel kernel launches of this process
+ *     so far (reset != 0 clears the count after reading it).
  * unet_linear_sum_assignment: scipy.optimize.linear_sum_assignment's
  *   minimisation on a row-major nr x nc fp64 cost matrix (host pointers,
  *   min(nr, nc) pairs sorted by row); -EINVAL for NaN / -inf / infeasible. */
@@ -324,6 +370,15 @@ int unet_tracker_step_host(unet_tracker* t, int frame, int n_curr, const int32_t
                            const int64_t* host_areas, const int64_t* host_inter);
 int unet_tracker_num_tracks(const unet_tracker* t);
 int unet_tracker_tracks(const unet_tracker* t, int32_t* host_out, int cap);
+enum { UNET_TRACK_SCOPE_SHARED = 0, UNET_TRACK_SCOPE_FRAME = 1 };
+int unet_tracker_set_label_scope(unet_tracker* t, int scope);
+int unet_tracker_num_frames(const unet_tracker* t);
+int unet_tracker_frame_map(const unet_tracker* t, int index, int32_t* host_frame, int32_t* host_labels,
+                           int32_t* host_track_ids, int cap);
+size_t unet_tracker_relabel_ws_bytes(int t, int h, int w);
+int unet_tracker_relabel(unet_tracker* t, const uint16_t* labels, const int32_t* host_frames, int n, uint16_t* out,
+                         void* ws, unet_stream_t stream);
+long long unet_tracker_relabel_launches(int reset);
 int unet_linear_sum_assignment(long long nr, long long nc, const double* host_cost, int64_t* host_row_ind,
                                int64_t* host_col_ind);
 

@@ -148,9 +148,48 @@ static void test_tracker() {
   const int32_t unsorted[] = {5, 2};
   CHECK(unet_tracker_step_host(t, 3, 2, unsorted, a0, nullptr) != 0);
   CHECK(unet_tracker_tracks(t, nullptr, 0) == n);
+  // frame maps: one per accepted step (the rejected one left none)
+  CHECK(unet_tracker_num_frames(t) == 3);
+  int32_t fr = -1, lab[3] = {0, 0, 0}, ids[3] = {0, 0, 0};
+  CHECK(unet_tracker_frame_map(t, 1, &fr, lab, ids, 3) == 3 && fr == 1);
+  CHECK(lab[0] == 3 && lab[1] == 4 && lab[2] == 5 && ids[0] == 1 && ids[1] == 3 && ids[2] == 4);
+  CHECK(unet_tracker_frame_map(t, 0, nullptr, nullptr, ids, 1) == 2 && ids[0] == 1 && ids[1] == 3);
+  CHECK(unet_tracker_frame_map(t, 2, &fr, nullptr, nullptr, 0) == 0 && fr == 2);
+  CHECK(unet_tracker_frame_map(t, 3, nullptr, nullptr, nullptr, 0) == -EINVAL);
+  CHECK(unet_tracker_frame_map(t, -1, nullptr, nullptr, nullptr, 0) == -EINVAL);
+  CHECK(unet_tracker_set_label_scope(t, UNET_TRACK_SCOPE_FRAME) == -EBUSY);
+  // relabel's errors come from the host maps: the pointers are never touched
+  uint16_t* dummy = reinterpret_cast<uint16_t*>(uintptr_t(0x10000));
+  const int32_t absent[] = {9};
+  CHECK(unet_tracker_relabel(t, dummy, absent, 1, dummy, dummy, nullptr) == -ENOENT);
+  CHECK(std::strstr(unet_last_error(), "frame 9") != nullptr);
+  CHECK(unet_tracker_relabel(t, nullptr, absent, 1, dummy, dummy, nullptr) == -EINVAL);
+  CHECK(unet_tracker_relabel(t, dummy, absent, 0, dummy, dummy, nullptr) == 0);
+  CHECK(unet_tracker_relabel_ws_bytes(2, 8, 8) == 2 * 65536 * 2 && unet_tracker_relabel_ws_bytes(0, 8, 8) == 0);
   unet_tracker_destroy(t);
   CHECK(unet_tracker_create(0, 8, 0.3, 0.1, 2) == nullptr);
   unet_tracker_destroy(nullptr);
+  // the two label scopes on the reference's quirk: previous objects 3 and 4, current 4 and 5,
+  // "previous 3 -> current 4" then "previous 4 -> current 5"
+  for (int scope = 0; scope < 2; ++scope) {
+    unet_tracker* s = unet_tracker_create(8, 8, 0.3, 0.1, 2);
+    CHECK(s != nullptr);
+    CHECK(unet_tracker_set_label_scope(s, 2) == -EINVAL);
+    CHECK(unet_tracker_set_label_scope(s, scope) == 0);
+    const int32_t p[] = {3, 4}, c[] = {4, 5};
+    const int64_t ar[] = {10, 10};
+    const int64_t in[] = {10, 0, 0, 10};  // 3 -> 4 and 4 -> 5, IoU 1 each
+    CHECK(unet_tracker_step_host(s, 0, 2, p, ar, nullptr) == 0);
+    CHECK(unet_tracker_step_host(s, 1, 2, c, ar, in) == 0);
+    int32_t l2[2], i2[2];
+    CHECK(unet_tracker_frame_map(s, 1, nullptr, l2, i2, 2) == 2 && l2[0] == 4 && l2[1] == 5);
+    // shared: current 4's entry replaces previous 4's, so the second link moves track 1 on to
+    // current 5 and current 4 is left without a track
+    if (scope == UNET_TRACK_SCOPE_SHARED) CHECK(i2[0] == 0 && i2[1] == 1);
+    else CHECK(i2[0] == 1 && i2[1] == 2);
+    CHECK(unet_tracker_num_tracks(s) == 2);
+    unet_tracker_destroy(s);
+  }
 }
 
 static void test_ctc() {

@@ -53,10 +53,12 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <atomic>
 #include <cerrno>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <map>
 #include <numeric>
 #include <string>
 #include <vector>
@@ -157,6 +159,76 @@ hipError_t overlap(const uint16_t* a, const uint16_t* b, int h, int w, void* ws,
   lb.assign(l1.begin() + 1, l1.end());
   return hipSuccess;
 }
+
+// ------------------------- track-labelled result masks -----------------------
+// out[f][p] = lut[f][labels[f][p]]: a pure stream, 2 bytes in and 2 bytes out
+// per pixel.  One launch covers the stack: workgroup b of a frame takes the
+// frame's 16-byte vectors [b * kRlVecPerWg, (b + 1) * kRlVecPerWg), four per
+// lane, all four loads issued before the first look-up.  Frame f starts at byte
+// 2 f h w of the stack, so its first pixels up to a 16-byte boundary ("head")
+// and the last < 8 ("tail") go through scalar accesses of workgroup 0; where
+// labels and out sit differently relative to 16 bytes the frame is relabelled
+// pixel by pixel.  Every pixel is read and written by the same lane, the read
+// first, so out == labels is safe.  The frame's table (lut_len uint16, a
+// multiple of 8, at a 16-byte boundary of the workspace) is staged in LDS when
+// it has at most kRlLdsLabels entries (16 KiB: eight workgroups of four waves,
+// as many as a CU's wave slots hold, take 128 of its 160 KiB) and read through
+// L2 otherwise; labels >= lut_len give 0.
+constexpr int kRlThreads = 256;
+constexpr int kRlVecPerLane = 4;
+constexpr int kRlVecPerWg = kRlThreads * kRlVecPerLane;
+constexpr unsigned kRlLdsLabels = 8192;
+
+typedef unsigned short rl_us8 __attribute__((ext_vector_type(8)));
+
+template <bool kLds>
+__global__ __launch_bounds__(kRlThreads) void k_tr_relabel(const uint16_t* in, uint16_t* out, size_t hw, unsigned bpf,
+                                                           const uint16_t* __restrict__ luts, unsigned lut_len) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t s_lut[];
+  const unsigned f = blockIdx.x / bpf, b = blockIdx.x % bpf, tid = threadIdx.x;
+  const uint16_t* lut = luts + (size_t)f * lut_len;
+  if (kLds) {
+    for (unsigned i = tid; i < lut_len / 8; i += kRlThreads)
+      reinterpret_cast<rl_us8*>(s_lut)[i] = reinterpret_cast<const rl_us8*>(lut)[i];
+    __syncthreads();
+  }
+  auto look = [&](unsigned v) -> uint16_t { return v < lut_len ? (kLds ? s_lut[v] : lut[v]) : (uint16_t)0; };
+  const uint16_t* fi = in + (size_t)f * hw;
+  uint16_t* fo = out + (size_t)f * hw;
+  const uintptr_t ai = reinterpret_cast<uintptr_t>(fi), ao = reinterpret_cast<uintptr_t>(fo);
+  if ((ai ^ ao) & 15) {  // no common 16-byte phase: scalar, strided over the frame's workgroups
+    for (size_t p = (size_t)b * kRlThreads + tid; p < hw; p += (size_t)bpf * kRlThreads) fo[p] = look(fi[p]);
+    return;
+  }
+  size_t head = ((16 - (ai & 15)) & 15) >> 1;
+  if (head > hw) head = hw;
+  const size_t nvec = (hw - head) / 8, tail = head + nvec * 8;
+  if (b == 0) {
+    if (tid < head) fo[tid] = look(fi[tid]);
+    if (tail + tid < hw) fo[tail + tid] = look(fi[tail + tid]);
+  }
+  const rl_us8* vi = reinterpret_cast<const rl_us8*>(fi + head);
+  rl_us8* vo = reinterpret_cast<rl_us8*>(fo + head);
+  const size_t v0 = (size_t)b * kRlVecPerWg + tid;
+  rl_us8 r[kRlVecPerLane];
+#pragma unroll
+  for (int k = 0; k < kRlVecPerLane; ++k) {
+    const size_t v = v0 + (size_t)k * kRlThreads;
+    if (v < nvec) r[k] = vi[v];
+  }
+#pragma unroll
+  for (int k = 0; k < kRlVecPerLane; ++k) {
+    const size_t v = v0 + (size_t)k * kRlThreads;
+    if (v < nvec) {
+      rl_us8 o;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) o[q] = look(r[k][q]);
+      vo[v] = o;
+    }
+  }
+}
+
+std::atomic<long long> g_relabel_launches{0};
 
 // --------------------------- linear sum assignment ---------------------------
 // Shortest augmenting path (Crouse 2016) as scipy implements it: columns are
@@ -271,6 +343,17 @@ struct unet_tracker {
   std::vector<long long> prev_area;
   bool first = true;
   bool has_prev_dev = false;        // the device copy of the previous frame is valid
+  // UNET_TRACK_SCOPE_FRAME: `active` holds the previous frame's labels only and
+  // the current frame's go to `active_next`; the two swap when the step ends
+  int scope = UNET_TRACK_SCOPE_SHARED;
+  std::vector<int> active_next;
+  struct FrameMap {
+    int frame;
+    std::vector<int> labels, ids;   // ascending labels; track id per label, 0 = none
+  };
+  std::vector<FrameMap> maps;       // one per step, in the order given
+  std::map<int, int> map_of_frame;  // frame number -> index of its last map
+  std::vector<uint16_t> lut_stage;  // unet_tracker_relabel's host tables (the upload's source)
   unet_tracker() : active(kLabels, -1) {}
 
   int new_track(int frame, int parent) {
@@ -283,8 +366,11 @@ struct unet_tracker {
   int step(int frame, const std::vector<int>& cur, const std::vector<long long>& area,
            const std::vector<long long>& inter) {
     const long long np = (long long)prev_labels.size(), nc = (long long)cur.size();
+    const bool scoped = scope == UNET_TRACK_SCOPE_FRAME;
+    if (scoped) active_next.assign(kLabels, -1);
+    std::vector<int>& now = scoped ? active_next : active;  // where current-frame labels are assigned
     if (first) {
-      for (int lab : cur) active[lab] = new_track(frame, -1);
+      for (int lab : cur) now[lab] = new_track(frame, -1);
       first = false;
     } else {
       auto iou_of = [&](long long i, long long j) -> double {
@@ -311,7 +397,7 @@ struct unet_tracker {
             const int tid = active[pl];
             tracks[tid - 1].end = frame;
             active[pl] = -1;
-            active[cl] = tid;
+            now[cl] = tid;
             mp[i] = 1;
             mc[j] = 1;
           }
@@ -335,14 +421,22 @@ struct unet_tracker {
           tracks[parent - 1].end = frame - 1;
           active[pl] = -1;
           for (long long j : kids) {
-            active[cur[j]] = new_track(frame, parent);
+            now[cur[j]] = new_track(frame, parent);
             mc[j] = 1;
           }
         }
       }
       for (long long j = 0; j < nc; ++j)  // new objects (:248-254)
-        if (!mc[j]) active[cur[j]] = new_track(frame, -1);
+        if (!mc[j]) now[cur[j]] = new_track(frame, -1);
     }
+    FrameMap m;
+    m.frame = frame;
+    m.labels = cur;
+    m.ids.reserve(cur.size());
+    for (int lab : cur) m.ids.push_back(std::max(now[lab], 0));
+    map_of_frame[frame] = (int)maps.size();
+    maps.push_back(std::move(m));
+    if (scoped) active.swap(active_next);
     prev_labels = cur;
     prev_area = area;
     return 0;
@@ -437,6 +531,101 @@ int unet_tracker_tracks(const unet_tracker* t, int32_t* out, int cap) {
     out[4 * q + 3] = tr.parent;
   }
   return (int)order.size();
+}
+
+int unet_tracker_set_label_scope(unet_tracker* t, int scope) {
+  if (!t || (scope != UNET_TRACK_SCOPE_SHARED && scope != UNET_TRACK_SCOPE_FRAME)) return -EINVAL;
+  if (!t->maps.empty()) return -EBUSY;
+  t->scope = scope;
+  return 0;
+}
+
+int unet_tracker_num_frames(const unet_tracker* t) { return t ? (int)t->maps.size() : -EINVAL; }
+
+int unet_tracker_frame_map(const unet_tracker* t, int index, int32_t* frame, int32_t* labels, int32_t* track_ids,
+                           int cap) {
+  if (!t || index < 0 || index >= (int)t->maps.size()) return -EINVAL;
+  const auto& m = t->maps[index];
+  if (frame) *frame = m.frame;
+  const int k = std::min(std::max(cap, 0), (int)m.labels.size());
+  for (int q = 0; q < k; ++q) {
+    if (labels) labels[q] = m.labels[q];
+    if (track_ids) track_ids[q] = m.ids[q];
+  }
+  return (int)m.labels.size();
+}
+
+size_t unet_tracker_relabel_ws_bytes(int t, int h, int w) {
+  return t > 0 && h > 0 && w > 0 ? ((size_t)t * kLabels * 2 + 255) / 256 * 256 : 0;
+}
+
+int unet_tracker_relabel(unet_tracker* t, const uint16_t* labels, const int32_t* host_frames, int n, uint16_t* out,
+                         void* ws, unet_stream_t stream) {
+  if (!t || n < 0) return -EINVAL;
+  if (n == 0) return 0;
+  if (!labels || !out || !host_frames || !ws || (reinterpret_cast<uintptr_t>(labels) & 1) ||
+      (reinterpret_cast<uintptr_t>(out) & 1) || (reinterpret_cast<uintptr_t>(ws) & 255)) {
+    unet::set_last_error("unet_tracker_relabel: null labels / frames / out / ws, labels or out not 2-byte aligned, or "
+                         "ws not 256-byte aligned");
+    return -EINVAL;
+  }
+  const size_t hw = (size_t)t->h * t->w;
+  const size_t bpf = std::max<size_t>(1, (hw / 8 + kRlVecPerWg - 1) / kRlVecPerWg);
+  if (bpf * (size_t)n > 0x7fffffffull) {
+    unet::set_last_error("unet_tracker_relabel: the stack needs more than 2^31 - 1 workgroups");
+    return -EINVAL;
+  }
+  // every error is found from the host maps, before any device call
+  std::vector<const unet_tracker::FrameMap*> maps((size_t)n);
+  int top = 0;
+  for (int i = 0; i < n; ++i) {
+    const auto it = t->map_of_frame.find(host_frames[i]);
+    if (it == t->map_of_frame.end()) {
+      unet::set_last_error("unet_tracker_relabel: frame " + std::to_string(host_frames[i]) +
+                           " was never given to this tracker");
+      return -ENOENT;
+    }
+    const auto& m = t->maps[it->second];
+    for (int id : m.ids)
+      if (id > 65535) {
+        unet::set_last_error("unet_tracker_relabel: frame " + std::to_string(m.frame) + " holds track id " +
+                             std::to_string(id) + ", above the 65535 a 16-bit mask carries");
+        return -ERANGE;
+      }
+    if (!m.labels.empty()) top = std::max(top, m.labels.back());
+    maps[i] = &m;
+  }
+  const unsigned lut_len = (unsigned)((top + 1 + 7) / 8 * 8);  // <= 65536
+  t->lut_stage.assign((size_t)n * lut_len, 0);
+  for (int i = 0; i < n; ++i) {
+    uint16_t* lut = t->lut_stage.data() + (size_t)i * lut_len;
+    for (size_t q = 0; q < maps[i]->labels.size(); ++q) lut[maps[i]->labels[q]] = (uint16_t)maps[i]->ids[q];
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  uint16_t* luts = reinterpret_cast<uint16_t*>(ws);
+  hipError_t e = hipMemcpyAsync(luts, t->lut_stage.data(), t->lut_stage.size() * 2, hipMemcpyHostToDevice, s);
+  // lut_stage is rewritten by the next call: the copy has left it before we return
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e == hipSuccess) {
+    const dim3 grid((unsigned)(bpf * (size_t)n));
+    if (lut_len <= kRlLdsLabels)
+      hipLaunchKernelGGL(k_tr_relabel<true>, grid, dim3(kRlThreads), lut_len * 2, s, labels, out, hw, (unsigned)bpf,
+                         luts, lut_len);
+    else
+      hipLaunchKernelGGL(k_tr_relabel<false>, grid, dim3(kRlThreads), 0, s, labels, out, hw, (unsigned)bpf, luts,
+                         lut_len);
+    g_relabel_launches.fetch_add(1);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) {
+    unet::set_last_error(std::string("unet_tracker_relabel: ") + hipGetErrorString(e));
+    return -EIO;
+  }
+  return 0;
+}
+
+long long unet_tracker_relabel_launches(int reset) {
+  return reset ? g_relabel_launches.exchange(0) : g_relabel_launches.load();
 }
 
 }  // extern "C"

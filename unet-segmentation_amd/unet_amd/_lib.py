@@ -93,6 +93,12 @@ SIGNATURES = {
     "unet_tracker_step_host": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "unet_tracker_num_tracks": (_i, [_vp]),
     "unet_tracker_tracks": (_i, [_vp, _vp, _i]),
+    "unet_tracker_set_label_scope": (_i, [_vp, _i]),
+    "unet_tracker_num_frames": (_i, [_vp]),
+    "unet_tracker_frame_map": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int32), _vp, _vp, _i]),
+    "unet_tracker_relabel_ws_bytes": (_sz, [_i, _i, _i]),
+    "unet_tracker_relabel": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "unet_tracker_relabel_launches": (ctypes.c_longlong, [_i]),
     "unet_linear_sum_assignment": (_i, [ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp]),
     "unet_ctc_create": (_vp, []),
     "unet_ctc_destroy": (None, [_vp]),
