@@ -229,6 +229,43 @@ int unet_elastic_deform_ex(const uint8_t* image, const uint16_t* labels, int n, 
                            uint8_t* target_out, uint8_t* image_out, uint16_t* ids_out, void* ws,
                            unet_stream_t stream);
 
+/* Training tiles over the whole frame: n augmented (th x tw) tiles cut from
+ * nframes resident (h x w) frames in one warp launch (plus the two Gaussian
+ * launches when an elastic field is given).  Sample s reads frame
+ * frame_idx[s] (clamped to [0, nframes)); its params row is
+ * a00 a01 b0 a10 a11 b1 gain bias.  For tile pixel (ty, tx), all in fp64 and
+ * in exactly this order, without fma contraction:
+ *   cy = ((a00*ty + a01*tx) + b0) + dy,  cx = ((a10*ty + a11*tx) + b1) + dx
+ *   dx|dy = the unet_elastic_deform field of noise (n, 2, th, tw) on the TILE
+ *          grid (field 0 -> dx, field 1 -> dy), or 0 when noise is NULL (no
+ *          Gaussian launch is made then and ws may be NULL);
+ *   extend 0: the coordinate is folded half-sample symmetric (scipy "reflect",
+ *          d c b a | a b c d | d c b a), as unet_elastic_deform does;
+ *   extend 1: whole-sample symmetric (scipy "mirror", np.pad "reflect",
+ *          d c b | a b c d | c b a: what unet_tile_gather feeds the network at
+ *          inference): m = fmod(c, 2n-2), + (2n-2) if negative, 2n-2-m if
+ *          m > n-1; a length-1 axis gives 0; the neighbour index floor(m)+1
+ *          and the nearest index floor(m+0.5) are clamped to n-1;
+ *   iv = uint8(bilinear image value), rounded as unet_elastic_deform does;
+ *   image_out (n, th, tw) uint8 (may be NULL) = iv;
+ *   x_out (n, th, tw) fp32 = (float)min(max(gain*iv + bias, 0), 255) / 255
+ *          (the intensity step acts on the rounded uint8; gain 1, bias 0 give
+ *          unet_elastic_deform's x);
+ *   target_out, ids_out (may be NULL): nearest label, as unet_elastic_deform_ex;
+ *   weight_out (n, th, tw) fp32 (may be NULL; needs weights (nframes, h, w)
+ *          fp32) = the weight plane at the same nearest index.
+ * ws >= unet_tile_warp_ws_bytes(n, th, tw), 8-byte aligned (the two Gaussian
+ * planes, as unet_elastic_ws_bytes; 0 for non-positive sizes).  Returns
+ * -EINVAL before any device call on non-positive sizes, weight_out without
+ * weights, extend outside {0, 1}, a NULL required pointer, and (with noise)
+ * sigma <= 0, a radius int(4 sigma + 0.5) > 128 (the Gaussian kernels' LDS
+ * rows) or a NULL / misaligned ws. */
+size_t unet_tile_warp_ws_bytes(int n, int th, int tw);
+int unet_tile_warp(const uint8_t* frames, const uint16_t* labels, const float* weights, int nframes, int h, int w,
+                   const int32_t* frame_idx, const double* params, int n, int th, int tw, int extend,
+                   const double* noise, double alpha, double sigma, float* x_out, uint8_t* target_out,
+                   uint8_t* image_out, uint16_t* ids_out, float* weight_out, void* ws, unet_stream_t stream);
+
 /* Overlap-tile inference (scripts/predict1.py:35-49
  * margin rule): tile t of an nx-wide tile grid has its input origin at
  * ((t / nx) * tile_out - top, (t % nx) * tile_out - left) in the image; a call

@@ -326,6 +326,24 @@ static void test_warp() {
   CHECK(std::strstr(unet_last_error(), "unet_split_instances") != nullptr);
   CHECK(unet_set_tuning("split_threads", 96) == -EINVAL && unet_set_tuning("split_threads", 128) == 0 &&
         unet_set_tuning("split_threads", -1) == 0);
+  // training tiles: rejected before any device call (the buffers are host memory)
+  CHECK(unet_tile_warp_ws_bytes(0, 4, 4) == 0 && unet_tile_warp_ws_bytes(2, 0, 4) == 0 &&
+        unet_tile_warp_ws_bytes(2, 4, -1) == 0 && unet_tile_warp_ws_bytes(3, 7, 5) == unet_elastic_ws_bytes(3, 7, 5));
+  alignas(8) double prm[8] = {1, 0, 0, 0, 1, 0, 1, 0};
+  alignas(8) double wsb[64];
+  const int32_t fi[1] = {0};
+  float xo[4], wo[4];
+  uint8_t to[4];
+  const double* nz = wsb;
+  CHECK(unet_tile_warp(p, lab, nullptr, 1, 2, 2, fi, prm, 1, 2, 2, 2, nullptr, 0, 1, xo, to, nullptr, nullptr, nullptr, nullptr, nullptr) == -EINVAL);   // extend
+  CHECK(unet_tile_warp(p, lab, nullptr, 1, 2, 2, fi, prm, 1, 2, 2, 1, nullptr, 0, 1, xo, to, nullptr, nullptr, wo, nullptr, nullptr) == -EINVAL);        // weight_out, no weights
+  CHECK(unet_tile_warp(p, lab, nullptr, 1, 2, 2, fi, prm, 1, 0, 2, 1, nullptr, 0, 1, xo, to, nullptr, nullptr, nullptr, nullptr, nullptr) == -EINVAL);   // th
+  CHECK(unet_tile_warp(p, lab, nullptr, 0, 2, 2, fi, prm, 1, 2, 2, 1, nullptr, 0, 1, xo, to, nullptr, nullptr, nullptr, nullptr, nullptr) == -EINVAL);   // nframes
+  CHECK(unet_tile_warp(p, lab, nullptr, 1, 2, 2, nullptr, prm, 1, 2, 2, 1, nullptr, 0, 1, xo, to, nullptr, nullptr, nullptr, nullptr, nullptr) == -EINVAL);
+  CHECK(unet_tile_warp(p, lab, nullptr, 1, 2, 2, fi, prm, 1, 2, 2, 0, nz, 10, 0.0, xo, to, nullptr, nullptr, nullptr, wsb, nullptr) == -EINVAL);         // sigma
+  CHECK(unet_tile_warp(p, lab, nullptr, 1, 2, 2, fi, prm, 1, 2, 2, 0, nz, 10, 40.0, xo, to, nullptr, nullptr, nullptr, wsb, nullptr) == -EINVAL);        // radius 160: LDS rows
+  CHECK(unet_tile_warp(p, lab, nullptr, 1, 2, 2, fi, prm, 1, 2, 2, 0, nz, 10, 2.0, xo, to, nullptr, nullptr, nullptr, nullptr, nullptr) == -EINVAL);     // no workspace
+  CHECK(std::strstr(unet_last_error(), "unet_tile_warp") != nullptr);
 }
 
 static void test_misc() {

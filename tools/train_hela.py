@@ -59,6 +59,13 @@ def build_parser():
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "bf16x3"])
     ap.add_argument("--weights", default="static", choices=["static", "warped", "border", "border-warped"])
     ap.add_argument("--no-augment", action="store_true")
+    ap.add_argument("--tiles", default="frame", choices=["frame", "mirror"],
+                    help="frame: warp whole frames, supervise the centre crop; mirror: input tiles whose output "
+                         "window lies anywhere in the frame, context mirrored as at inference (TileAugment)")
+    ap.add_argument("--rotate", type=float, default=0.0, metavar="DEG", help="--tiles mirror: rotation in +-DEG")
+    ap.add_argument("--flip", action="store_true", help="--tiles mirror: random horizontal / vertical flips")
+    ap.add_argument("--gain", type=float, default=0.0, metavar="G", help="--tiles mirror: contrast in 1 +- G")
+    ap.add_argument("--bias", type=float, default=0.0, metavar="B", help="--tiles mirror: brightness in +-B (0-255)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--checkpoint", default=None, help="save the best-val state_dict here")
     return ap
@@ -99,8 +106,16 @@ def main():
     bs = min(args.batch, len(tr_idx))
     trainer = Trainer(model, bs, h, w, lr=args.lr, momentum=0.99, precision=args.precision)
     sel = torch.as_tensor(tr_idx, device=dev)
+    tiles = None
+    if args.tiles == "mirror":
+        from unet_amd.augment import TileAugment
+        tiles = TileAugment((h, w), extend="mirror", elastic=not args.no_augment, max_rotate=args.rotate,
+                            flip=args.flip, gain=args.gain, bias=args.bias, out_hw=trainer.out_hw, seed=args.seed)
+    elif args.rotate or args.flip or args.gain or args.bias:
+        ap.error("--rotate / --flip / --gain / --bias need --tiles mirror")
     data = HeLaBatches(img_d.index_select(0, sel), lab_d.index_select(0, sel), bs, trainer.out_hw,
-                       augment=not args.no_augment, weights=args.weights, seed=args.seed, drop_last=True)
+                       augment=not args.no_augment, weights=args.weights, seed=args.seed, drop_last=True,
+                       tiles=tiles)
     crit = WeightedCrossEntropyLoss()
     best = float("inf")
     for epoch in range(args.epochs):
@@ -127,7 +142,7 @@ def main():
                 torch.save(model.state_dict(), args.checkpoint)
         print(json.dumps({"epoch": epoch + 1, "train_loss": round(train_loss, 6), "val_loss": val_loss,
                           "steps": len(losses), "images_per_s": round(len(losses) * bs / dt, 2),
-                          "augment": not args.no_augment, "weights": args.weights,
+                          "augment": not args.no_augment, "weights": args.weights, "tiles": args.tiles,
                           "precision": args.precision}), flush=True)
 
 

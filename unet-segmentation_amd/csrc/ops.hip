@@ -701,6 +701,42 @@ int unet_elastic_deform(const uint8_t* image, const uint16_t* labels, int n, int
                                 st);
 }
 
+size_t unet_tile_warp_ws_bytes(int n, int th, int tw) {
+  return n > 0 && th > 0 && tw > 0 ? elastic_ws_bytes(n, th, tw) : 0;
+}
+
+int unet_tile_warp(const uint8_t* frames, const uint16_t* labels, const float* weights, int nframes, int h, int w,
+                   const int32_t* frame_idx, const double* params, int n, int th, int tw, int extend,
+                   const double* noise, double alpha, double sigma, float* x_out, uint8_t* target_out,
+                   uint8_t* image_out, uint16_t* ids_out, float* weight_out, void* ws, unet_stream_t st) {
+  // every check runs on the host, before the first device call
+  if (!tile_warp_check(nframes, h, w, n, th, tw, extend, noise != nullptr, sigma)) {
+    set_last_error("unet_tile_warp: need nframes, h, w, n, th, tw >= 1, extend 0 (reflect) or 1 (mirror) and, with an "
+                   "elastic field, sigma > 0 with radius int(4 sigma + 0.5) <= 128");
+    return -EINVAL;
+  }
+  if (!frames || !labels || !frame_idx || !params || !x_out || !target_out) {
+    set_last_error("unet_tile_warp: null frames / labels / frame_idx / params / x_out / target_out");
+    return -EINVAL;
+  }
+  if (weight_out && !weights) {
+    set_last_error("unet_tile_warp: weight_out needs the weights planes");
+    return -EINVAL;
+  }
+  if (noise && (!ws || (reinterpret_cast<uintptr_t>(ws) & 7))) {
+    set_last_error("unet_tile_warp: the elastic field needs an 8-byte aligned ws of unet_tile_warp_ws_bytes");
+    return -EINVAL;
+  }
+  const hipError_t e = launch_tile_warp(frames, labels, weights, nframes, h, w, frame_idx, params, n, th, tw, extend,
+                                        noise, alpha, sigma, x_out, target_out, image_out, ids_out, weight_out, ws,
+                                        reinterpret_cast<hipStream_t>(st));
+  if (e != hipSuccess) {
+    set_last_error(std::string("unet_tile_warp: ") + hipGetErrorString(e));
+    return e == hipErrorInvalidValue ? -EINVAL : -EIO;
+  }
+  return 0;
+}
+
 int unet_mask_from_logits(const float* logits, uint8_t* mask, int n, int h, int w, unet_stream_t st) {
   OPCK(launch_mask(logits, mask, n, h, w, reinterpret_cast<hipStream_t>(st)));
   return 0;

@@ -442,6 +442,13 @@ size_t elastic_ws_bytes(int n, int h, int w);
 hipError_t launch_elastic(const uint8_t* img, const uint16_t* lab, int n, int h, int w, const double* noise,
                           double alpha, double sigma, float* x_out, uint8_t* t_out, uint8_t* img_out, uint16_t* ids_out,
                           void* ws, hipStream_t s);
+// training tiles: affine + elastic warp of (th x tw) tiles out of resident frames (k_tile_warp).
+// tile_warp_check is the host-side argument check (no device call); launch_tile_warp runs it first
+bool tile_warp_check(int nframes, int h, int w, int n, int th, int tw, int extend, bool elastic, double sigma);
+hipError_t launch_tile_warp(const uint8_t* frames, const uint16_t* labels, const float* weights, int nframes, int h,
+                            int w, const int32_t* frame_idx, const double* params, int n, int th, int tw, int extend,
+                            const double* noise, double alpha, double sigma, float* x_out, uint8_t* t_out,
+                            uint8_t* img_out, uint16_t* ids_out, float* w_out, void* ws, hipStream_t s);
 
 // inc.c0: Ci in {1,2,3,4} direct conv from an NCHW input; y NHWC (Co = 64 multiple).
 hipError_t launch_conv_first_fwd(const float* x_nchw, int n, int ci, int h, int w,

@@ -64,6 +64,9 @@ SIGNATURES = {
                                  _vp]),
     "unet_elastic_deform_ex": (_i, [_vp, _vp, _i, _i, _i, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp,
                                     _vp, _vp]),
+    "unet_tile_warp_ws_bytes": (_sz, [_i, _i, _i]),
+    "unet_tile_warp": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_double,
+                            ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "unet_conv3x3_fwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "unet_conv3x3_dgrad": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "unet_conv3x3_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -17,6 +17,10 @@ device, and gathers them per batch.  ``weights="border"`` and
 ``"border-warped"`` are the same two choices with the U-Net paper's
 border-aware maps (``weight_maps(mode="border")``: exact distances to the two
 nearest cells), the latter on the warped instance ids of each batch.
+``tiles=TileAugment(...)`` trains as the paper (and ``TileFarm``) predicts: each
+sample is an input tile whose output window lies anywhere in its frame, the
+missing context mirrored, so every labelled pixel reaches the loss instead of
+the central (out / frame)^2 of them.
 Shuffling and rank sharding follow DataLoader(shuffle=True) /
 DistributedSampler (unet_amd.dist.ShardedIndices).
 
@@ -29,7 +33,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .augment import ElasticDeform, weight_maps
+from .augment import ElasticDeform, TileAugment, weight_maps
 from .dist import ShardedIndices
 
 
@@ -56,7 +60,8 @@ class HeLaBatches:
     reference's un-augmented path (x = image / 255, target = label > 0)."""
 
     def __init__(self, images, labels, batch, out_hw, augment=True, alpha=2000.0, sigma=20.0, noise="device",
-                 weights="static", shuffle=True, seed=0, world=1, rank=0, drop_last=False, generator=None):
+                 weights="static", shuffle=True, seed=0, world=1, rank=0, drop_last=False, generator=None,
+                 tiles=None):
         if images.device.type != "cuda" or labels.device.type != "cuda":
             raise ValueError("HeLaBatches keeps its frames on the HIP device (no CPU fallback)")
         if images.dtype != torch.uint8 or images.dim() != 3 or tuple(labels.shape) != tuple(images.shape):
@@ -83,6 +88,18 @@ class HeLaBatches:
         self.static_w = (weight_maps(self.labels, mode="border" if weights == "border" else "reference")
                          if weights in ("static", "border") else None)
         self._lut = None
+        # tiles: a TileAugment cuts each sample anywhere in its frame (mirrored
+        # context, shift / rotation / flips / gray values) in place of the
+        # whole-frame warp; its output window is this object's out_hw
+        self.tiles = tiles
+        if tiles is not None:
+            if not isinstance(tiles, TileAugment):
+                raise ValueError("tiles must be a unet_amd.augment.TileAugment (or None: whole frames)")
+            if tiles.out_hw is None:
+                tiles.out_hw = self.out_hw
+            if tuple(tiles.out_hw) != self.out_hw:
+                raise ValueError(f"tiles.out_hw {tiles.out_hw} differs from out_hw {self.out_hw}")
+            tiles.shift_range(tuple(images.shape[1:]))  # raises when the window exceeds the tile
 
     def set_epoch(self, epoch):
         self.sampler.set_epoch(epoch)
@@ -91,9 +108,27 @@ class HeLaBatches:
         n = len(self.sampler)
         return n // self.batch if self.drop_last else (n + self.batch - 1) // self.batch
 
-    def make_batch(self, idx, seeds=None, noise=None):
+    def _make_tile_batch(self, idx, params, noise):
+        """The tiles= path: one unet_tile_warp call on the resident frames (the
+        batch's indices go to the kernel; no index_select copy of the frames)."""
+        if self.weights in ("static", "border"):  # the precomputed maps travel with the tile
+            x, t8, w = self.tiles(self.images, self.labels, idx, params=params, noise=noise, weights=self.static_w)
+        elif self.weights == "border-warped":
+            x, t8, ids = self.tiles(self.images, self.labels, idx, params=params, noise=noise, return_ids=True)
+            w = weight_maps(ids, mode="border")
+        else:
+            x, t8 = self.tiles(self.images, self.labels, idx, params=params, noise=noise)
+            w = weight_maps(t8[:, 0].to(torch.int16).view(torch.uint16))
+        target = center_crop_views(t8.to(torch.int64), self.out_hw)
+        weight = center_crop_views(w.unsqueeze(1), self.out_hw)
+        return x, target, weight
+
+    def make_batch(self, idx, seeds=None, noise=None, params=None):
         """One minibatch of the frames `idx` (list of ints).  `seeds` (numpy
-        noise) or `noise` ((B, 2, H, W) fp64) fix the elastic fields."""
+        noise) or `noise` ((B, 2, H, W) fp64) fix the elastic fields; with
+        tiles=, `params` ((B, 8)) and `noise` ((B, 2, th, tw)) fix the draw."""
+        if self.tiles is not None:
+            return self._make_tile_batch(idx, params, noise)
         dev = self.images.device
         sel = torch.as_tensor(np.asarray(idx, dtype=np.int64), device=dev)
         img, lab = self.images.index_select(0, sel), self.labels.index_select(0, sel)
