@@ -282,6 +282,41 @@ int unet_tile_gather(const float* image, int c, int h, int w, int tile_in, int t
 int unet_tile_scatter(const float* tile_logits, int k, int tile_out, int nx, int first, int stride, int ntiles,
                       int h, int w, float* logits, uint8_t* mask, unet_stream_t stream);
 
+/* Sequence inference with symmetry averaging (scripts/predict.py's step on
+ * whole frames).  A symmetry code s = r + 4 f (0..7) names
+ * S_s(x) = rot90(flip_f(x), r): f = 1 reverses the last axis first, then r
+ * quarter turns as torch.rot90(x, r, (-2, -1)).  `work` (ngroups, 2) int32 on
+ * the DEVICE holds one (frame, tile) pair per group, the tile numbered as for
+ * unet_tile_gather; `codes` is a HOST array of ns codes (1 <= ns <= 8), read
+ * during the call.  A group whose frame is outside [0, nframes) or whose tile
+ * is negative is skipped.
+ * unet_seq_tile_gather: frames (nframes, c, h, w), uint8 (frames_u8 != 0) or
+ *   fp32.  tiles (ngroups * ns, c, tile_in, tile_in) fp32: entry g * ns + j is
+ *   S_{codes[j]} of the mirror-folded tile of group g (as unet_tile_gather
+ *   reads it).  uint8 values are normalised ((v / 255) - 0.5) / 0.5 in fp32
+ *   with a correctly rounded division (torchvision's ToTensor + Normalize(0.5,
+ *   0.5) bit for bit); fp32 values are copied.
+ * unet_seq_tile_reduce: tile_logits (ngroups * ns, k, tile_out, tile_out).  Per
+ *   output pixel of a group, for j ascending, the k logits at the position
+ *   S_{codes[j]} moved the pixel to give a max-subtracted softmax (expf, sum
+ *   over classes ascending, division); the softmaxes are summed in that order
+ *   and multiplied by 1 / ns.  Outputs (each may be NULL, not all):
+ *   prob (nframes, k, h, w) fp32; mask (nframes, h, w) uint8 =
+ *   255 * (mean p1 > threshold), k == 2 only, decided as l1 > l0 when ns == 1
+ *   and threshold == 0.5 (unet_tile_scatter's rule, same bits); logits
+ *   (nframes, k, h, w), the mapped-back logits, ns == 1 only.  Every output
+ *   pixel is written once by one thread (no atomics); pixels past the frame are
+ *   dropped, pixels of no listed tile are left untouched.
+ * Both return an error, with nothing launched, on non-positive sizes,
+ * tile_in < tile_out, ns outside 1..8, a code outside 0..7, c or ngroups above
+ * 65535, a mask with k != 2, logits with ns != 1, or no output. */
+int unet_seq_tile_gather(const void* frames, int frames_u8, int nframes, int c, int h, int w, int tile_in,
+                         int tile_out, int top, int left, int nx, const int32_t* work, int ngroups,
+                         const int32_t* codes, int ns, float* tiles, unet_stream_t stream);
+int unet_seq_tile_reduce(const float* tile_logits, int k, int tile_out, int nx, const int32_t* work, int ngroups,
+                         const int32_t* codes, int ns, int nframes, int h, int w, float threshold, float* prob,
+                         uint8_t* mask, float* logits, unet_stream_t stream);
+
 /* Loss weight maps (scripts/preprocess_data.py:17-77 with
  * w0, sigma as its :14-15 = 10, 5): per sample of labels (n, h, w) uint16,
  * weights = fp32(wc) + w0 * exp(-(d1 + d2)^2 / (2 (sigma^2 + 1e-8))) where wc =

@@ -344,6 +344,23 @@ static void test_warp() {
   CHECK(unet_tile_warp(p, lab, nullptr, 1, 2, 2, fi, prm, 1, 2, 2, 0, nz, 10, 40.0, xo, to, nullptr, nullptr, nullptr, wsb, nullptr) == -EINVAL);        // radius 160: LDS rows
   CHECK(unet_tile_warp(p, lab, nullptr, 1, 2, 2, fi, prm, 1, 2, 2, 0, nz, 10, 2.0, xo, to, nullptr, nullptr, nullptr, nullptr, nullptr) == -EINVAL);     // no workspace
   CHECK(std::strstr(unet_last_error(), "unet_tile_warp") != nullptr);
+  // sequence inference: rejected before any device call (the buffers are host memory)
+  const int32_t wk[2] = {0, 0}, c01[2] = {0, 1}, c08[2] = {0, 8}, cneg[1] = {-1}, c9[9] = {0, 1, 2, 3, 4, 5, 6, 7, 0};
+  float tl[16], pr[16];
+  CHECK(unet_seq_tile_gather(p, 1, 1, 1, 2, 2, 1, 2, 0, 0, 1, wk, 1, c01, 2, tl, nullptr) == -EINVAL);   // tile_in < tile_out
+  CHECK(unet_seq_tile_gather(p, 1, 1, 1, 2, 2, 2, 1, 0, 0, 1, wk, 1, c08, 2, tl, nullptr) == -EINVAL);   // code 8
+  CHECK(unet_seq_tile_gather(p, 1, 1, 1, 2, 2, 2, 1, 0, 0, 1, wk, 1, cneg, 1, tl, nullptr) == -EINVAL);  // code -1
+  CHECK(unet_seq_tile_gather(p, 1, 1, 1, 2, 2, 2, 1, 0, 0, 1, wk, 1, c01, 0, tl, nullptr) == -EINVAL);   // ns 0
+  CHECK(unet_seq_tile_gather(p, 1, 1, 1, 2, 2, 2, 1, 0, 0, 1, wk, 1, c9, 9, tl, nullptr) == -EINVAL);    // ns 9
+  CHECK(unet_seq_tile_gather(p, 1, 0, 1, 2, 2, 2, 1, 0, 0, 1, wk, 1, c01, 2, tl, nullptr) == -EINVAL);   // nframes
+  CHECK(unet_seq_tile_gather(p, 1, 1, 1, 2, 2, 2, 1, 0, 0, 1, wk, 0, c01, 2, tl, nullptr) == -EINVAL);   // ngroups
+  CHECK(unet_seq_tile_gather(p, 1, 1, 1, 2, 2, 2, 1, 0, 0, 1, nullptr, 1, c01, 2, tl, nullptr) == -EINVAL);
+  CHECK(unet_seq_tile_reduce(tl, 3, 2, 1, wk, 1, c01, 2, 1, 2, 2, 0.5f, pr, to, nullptr, nullptr) == -EINVAL);       // mask, k = 3
+  CHECK(unet_seq_tile_reduce(tl, 2, 2, 1, wk, 1, c01, 2, 1, 2, 2, 0.5f, nullptr, nullptr, nullptr, nullptr) == -EINVAL);  // no output
+  CHECK(unet_seq_tile_reduce(tl, 2, 2, 1, wk, 1, c01, 2, 1, 2, 2, 0.5f, nullptr, nullptr, pr, nullptr) == -EINVAL);  // logits, ns = 2
+  CHECK(unet_seq_tile_reduce(tl, 2, 2, 1, wk, 1, c08, 2, 1, 2, 2, 0.5f, pr, nullptr, nullptr, nullptr) == -EINVAL);  // code 8
+  CHECK(unet_seq_tile_reduce(tl, 2, 0, 1, wk, 1, c01, 2, 1, 2, 2, 0.5f, pr, nullptr, nullptr, nullptr) == -EINVAL);  // tile_out
+  CHECK(unet_seq_tile_reduce(tl, 2, 2, 1, wk, 1, c01, 2, 1, 2, 0, 0.5f, pr, nullptr, nullptr, nullptr) == -EINVAL);  // w
 }
 
 static void test_misc() {

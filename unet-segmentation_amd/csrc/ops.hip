@@ -633,6 +633,24 @@ int unet_tile_scatter(const float* tile_logits, int k, int tile_out, int nx, int
   return 0;
 }
 
+int unet_seq_tile_gather(const void* frames, int frames_u8, int nframes, int c, int h, int w, int tile_in,
+                         int tile_out, int top, int left, int nx, const int32_t* work, int ngroups,
+                         const int32_t* codes, int ns, float* tiles, unet_stream_t st) {
+  if (!frames || !work || !codes || !tiles) return -EINVAL;
+  OPCK(launch_seq_tile_gather(frames, frames_u8, nframes, c, h, w, tile_in, tile_out, top, left, nx, work, ngroups,
+                              codes, ns, tiles, reinterpret_cast<hipStream_t>(st)));
+  return 0;
+}
+
+int unet_seq_tile_reduce(const float* tile_logits, int k, int tile_out, int nx, const int32_t* work, int ngroups,
+                         const int32_t* codes, int ns, int nframes, int h, int w, float threshold, float* prob,
+                         uint8_t* mask, float* logits, unet_stream_t st) {
+  if (!tile_logits || !work || !codes) return -EINVAL;
+  OPCK(launch_seq_tile_reduce(tile_logits, k, tile_out, nx, work, ngroups, codes, ns, nframes, h, w, threshold, prob,
+                              mask, logits, reinterpret_cast<hipStream_t>(st)));
+  return 0;
+}
+
 size_t unet_instance_masks_ws_bytes(int n, int h, int w) {
   return n > 0 && h > 0 && w > 0 ? instance_masks_ws_bytes(n, h, w) : 0;
 }

@@ -378,6 +378,16 @@ hipError_t launch_tile_gather(const float* img, int c, int h, int w, int ti, int
 hipError_t launch_tile_scatter(const float* lt, int k, int to, int nx, int first, int stride, int ntiles, int h,
                                int w, float* full, uint8_t* mask, hipStream_t s);
 
+// sequence inference with symmetry averaging (predict.hip).  work (ngroups, 2)
+// int32 on the device: (frame, tile) per group; codes: ns symmetry codes on
+// the host (s = r + 4 f: rot90(flip_f(x), r)), passed to the kernels by value.
+hipError_t launch_seq_tile_gather(const void* frames, int is_u8, int nframes, int c, int h, int w, int ti, int to,
+                                  int top, int left, int nx, const int32_t* work, int ngroups, const int32_t* codes,
+                                  int ns, float* tiles, hipStream_t s);
+hipError_t launch_seq_tile_reduce(const float* lt, int k, int to, int nx, const int32_t* work, int ngroups,
+                                  const int32_t* codes, int ns, int nframes, int h, int w, float threshold,
+                                  float* prob, uint8_t* mask, float* logits, hipStream_t s);
+
 // post-processing (postproc.hip)
 size_t instance_masks_ws_bytes(int n, int h, int w);
 hipError_t launch_instance_masks(const uint8_t* mask, int n, int h, int w, int min_size, uint16_t* out, void* ws,

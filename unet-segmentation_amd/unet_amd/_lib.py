@@ -51,6 +51,8 @@ SIGNATURES = {
     "unet_mask_from_logits": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "unet_tile_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "unet_tile_scatter": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "unet_seq_tile_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "unet_seq_tile_reduce": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "unet_instance_masks_ws_bytes": (_sz, [_i, _i, _i]),
     "unet_instance_masks": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "unet_rand_index_ws_bytes": (_sz, [_i, _i]),
@@ -189,7 +191,7 @@ def stream_of(device=None):
 _HASHED = ["igemm.hip", "igemm_bf16.hip", "conv3_dma.hip", "conv3_ring.hip", "winograd.hip", "elementwise.hip", "elastic.hip",
            "tiling.hip", "weightmap.hip", "postproc.hip", "track.hip", "ops.hip", "plan.hip", "wgrad3_ring.hip",
            "conv3_ring_pt.hip", "peak.hip", "gemm_ring.hip", "wgradT_ring.hip", "conv3_flat.hip", "conv3_c64.hip", "gemm_ring_p1.hip",
-           "gemm_ring_p2.hip", "wgrad_plane.hip", "igemm_plane.hip", "ctc.hip", "warp.hip", "split.hip", "unet_internal.h", "gemm_common.h", "ring_common.h", "conv3_ring_kernel.h",
+           "gemm_ring_p2.hip", "wgrad_plane.hip", "igemm_plane.hip", "ctc.hip", "warp.hip", "split.hip", "predict.hip", "unet_internal.h", "gemm_common.h", "ring_common.h", "conv3_ring_kernel.h",
            os.path.join("..", "..", "include", "unet_hip.h")]
 
 
