@@ -671,6 +671,12 @@ int unet_split_instances(const uint8_t* mask, const uint8_t* markers, int n, int
  *                  the BN+ReLU transform; padded dY bf16), as a bf16 plan
  *                  does -- the configuration the 61-66 tiles (bf16-stored A
  *                  only) run in; 0 (default) = fp32 A.
+ *  "op_strict"     1 = a per-op GEMM entry point (unet_conv3x3_fwd / _dgrad,
+ *                  unet_convT2_fwd / _bwd, unet_gemm_site_run) whose forced tile
+ *                  ("igemm_variant" > 0, or the descriptor's tile / split)
+ *                  does not apply to the call returns -EINVAL before it
+ *                  launches anything; 0 (default) = the built-in tile runs in
+ *                  its place, silently.  Tests set it to know which tile ran.
  *  "deterministic" 1 (or env UNET_DETERMINISTIC=1; default 0) = every weight
  *                  gradient runs a variant without fp32 atomics (slab
  *                  partials summed in a fixed order) and inc.c0's slab
@@ -838,6 +844,82 @@ int unet_conv1x1_fwd(const float* x, int n, int h, int w, int c, const float* wt
                      float* logits_nchw, unet_stream_t stream);
 int unet_conv1x1_bwd(const float* x, const float* dlogits_nchw, int n, int h, int w, int c, const float* wt, int k,
                      float* dx, float* dw, float* db, void* ws, unet_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * One forward / input-gradient GEMM of the network plan, with everything the
+ * plan fuses into it at that launch site (for per-element tests and tools).
+ * The entry point builds the arguments the plan builds there and runs them on
+ * the forced tile, the "igemm_variant" knob's tile, or the built-in choice.
+ *
+ *  site        GEMM rows (n, h, w)   src0                       fused
+ *  F_PLAIN     3x3 conv output grid  (n, h+2, w+2, ci)          scale0/shift0 (BN+ReLU on load), bias, stats
+ *  F_CAT       3x3 conv output grid  skip (n, skip_h, skip_w, c_split) read at origin (oy, ox), its own
+ *                                    scale0/shift0; src1 (n, h+2, w+2, ci - c_split), scale1/shift1
+ *                                    normally NULL; bias, stats
+ *  F_EVAL      as F_PLAIN            (n, h+2, w+2, ci)          bias, ReLU on store, no statistics
+ *  D_POOL      3x3 conv input grid   padded dY (n, h+2, w+2, co), read at origin 0     plain store
+ *  D_MASK      as D_POOL             as D_POOL                  ReLU mask from yref, bstats
+ *  D_SPLIT     as D_POOL             as D_POOL                  columns < n_split -> dst0 (C = n_split),
+ *                                                               the rest -> dst1 (C = ci - n_split), colsum1
+ *  T_FWD       convT input grid      (n, h, w, ci)              pixel shuffle to dst0 (n, 2h, 2w, co), bias
+ *  T_MASK      convT input grid      dY (n, 2h, 2w, co)         2x2 stride-2 gather; mask + bstats as D_MASK
+ *
+ * wt is torch's weight: conv (co, ci, 3, 3), ConvTranspose2d (ci, co, 2, 2).
+ * Forward sites produce co columns, D_* / T_MASK ci columns, T_FWD 4 co.
+ * dst0 / dst1 / yref live on the row grid (T_FWD: dst0 on the 2h x 2w grid).
+ * Every tensor is fp32 NHWC in the caller's buffers, except: with
+ * "op_precision" UNET_PREC_BF16 and "op_a16" 1 the entry point rounds the
+ * sources and yref to bf16 copies in ws (what a bf16 plan stores) and dst0 /
+ * dst1 ARE bf16 (2 bytes per element).  stats / bstats receive the raw
+ * [64][columns of dst0][2] fp64 partial sums (sum, sum of squares; sum dz',
+ * sum dz' * xhat), colsum1 the [64][columns of dst1] sums; the entry point
+ * zeroes them.  Channel counts are multiples of 8 (16 for every tile but the
+ * fused F(2x2) Winograd ones), column counts and n_split multiples of 32.
+ * tile: > 0 forces that tile of the igemm table, -1 = the "igemm_variant"
+ * knob, else the built-in choice.  split: K slices (<= 1: none); the partial
+ * planes live in ws.  With "op_strict" 1 a forced tile or split that does not
+ * apply is -EINVAL before anything is launched. */
+enum {
+  UNET_SITE_F_PLAIN = 0, UNET_SITE_F_CAT = 1, UNET_SITE_F_EVAL = 2, UNET_SITE_D_POOL = 3,
+  UNET_SITE_D_MASK = 4, UNET_SITE_D_SPLIT = 5, UNET_SITE_T_FWD = 6, UNET_SITE_T_MASK = 7
+};
+typedef struct unet_gemm_site {
+  int site;
+  int n, h, w;                 /* row grid of the GEMM */
+  int ci, co;                  /* the layer's channels (as in wt) */
+  int c_split;                 /* F_CAT: channels of src0 */
+  int skip_h, skip_w, oy, ox;  /* F_CAT: stored grid of src0, crop origin */
+  int n_split;                 /* D_SPLIT: columns of dst0 */
+  int tile, split;
+  const float* src0;
+  const float* src1;
+  const float* scale0;
+  const float* shift0;
+  const float* scale1;
+  const float* shift1;
+  const float* wt;
+  const float* bias;
+  void* dst0;
+  void* dst1;
+  const float* yref;
+  const float* bn_scale;
+  const float* bn_shift;
+  const float* bn_mean;
+  const float* bn_invstd;
+  double* stats;
+  double* bstats;
+  double* colsum1;
+} unet_gemm_site;
+/* Host only (no device call): 0 when unet_gemm_site_run would launch the
+ * descriptor as it stands (same checks, same knobs), -EINVAL otherwise.
+ * *tile (may be NULL) receives the tile id it would run. */
+int unet_gemm_site_check(const unet_gemm_site* d, int* tile);
+size_t unet_gemm_site_ws_bytes(const unet_gemm_site* d);
+int unet_gemm_site_run(const unet_gemm_site* d, void* ws, unet_stream_t stream);
+/* Host only: the rows of the igemm tile table.  Writes up to cap rows of 6 ints
+ * (id, family (IgemmFamily's order), bf16, x3, ksplit, wino_m) into out (may
+ * be NULL) and returns the number of rows of the table. */
+int unet_igemm_tile_table(int* out, int cap);
 
 /* Ceilings of this device, measured (bench.py's untimed tail; BASELINE.md asks
  * for roofline fractions against peaks measured on the box): kind 0 = dense

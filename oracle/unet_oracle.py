@@ -473,6 +473,173 @@ def center_crop_target(t, th, tw):
 
 
 # ----------------------------------------------------------------------------
+# GEMM launch sites of the plan (csrc/plan.hip run_forward / run_backward): one
+# forward or input-gradient GEMM with what the plan fuses into it, composed from
+# the primitives above.  `conv(x, w)` is the valid 3x3 correlation without bias
+# the site runs on (default: conv_valid_fwd in the inputs' precision; the tests
+# pass winograd_conv to measure a Winograd algorithm's own rounding).
+# Statistics are the per-column sums the epilogues collect: (sum y, sum y^2)
+# for a forward BatchNorm, (sum dz', sum dz' * xhat) for its backward,
+# xhat = (yref - mean) * invstd, and the column sums of a second destination.
+# ----------------------------------------------------------------------------
+def _conv_nobias(x, w):
+    return conv_valid_fwd(x, w, np.zeros(w.shape[0], x.dtype))
+
+
+def bn_relu_on_load(x, scale, shift, fma32=False):
+    """relu(x * scale + shift) as a consumer applies it when it reads x (None:
+    identity).  fma32: the product-sum rounded once to float32, as the kernels'
+    fmaf does, for operands that are rounded again afterwards (bf16)."""
+    if scale is None:
+        return x
+    z = x * scale + shift
+    if fma32:
+        z = np.asarray(z, np.float32).astype(np.float64)
+    return np.maximum(z, 0)
+
+
+def column_sums(y):
+    """(sum, sum of squares) per channel over (N,H,W): what bn_train_fwd's mean and
+    variance are made of."""
+    f = y.reshape(-1, y.shape[-1])
+    return f.sum(0), (f * f).sum(0)
+
+
+def bn_bwd_sums(dz, yref, mean, invstd):
+    """(sum dz, sum dz * xhat) per channel: bn_train_bwd's dbeta and dgamma."""
+    c = dz.shape[-1]
+    return dz.reshape(-1, c).sum(0), (dz * ((yref - mean) * invstd)).reshape(-1, c).sum(0)
+
+
+def site_f_plain(x, scale, shift, w, b, conv=_conv_nobias):
+    """Second conv of a DoubleConv (models/unet_model.py:15 after :12-13):
+    conv3x3(relu(bn(x))) + b with the BatchNorm statistics of the result.
+    Returns y, (sum y, sum y^2)."""
+    y = conv(bn_relu_on_load(x, scale, shift), w) + b
+    return y, column_sums(y)
+
+
+def site_f_cat(skip, scale0, shift0, oy, ox, up, w, b, scale1=None, shift1=None, conv=_conv_nobias):
+    """First conv of an Up block (models/unet_model.py:131 torch.cat([skip, up], 1)
+    then :11): the skip is read through its own BatchNorm+ReLU from a larger
+    stored grid at origin (oy, ox), `up` as it is.  Returns y, (sum y, sum y^2)."""
+    hh, ww = up.shape[1], up.shape[2]
+    a = bn_relu_on_load(skip, scale0, shift0)[:, oy:oy + hh, ox:ox + ww, :]
+    y = conv(np.concatenate([a, bn_relu_on_load(up, scale1, shift1)], -1), w) + b
+    return y, column_sums(y)
+
+
+def site_f_eval(x, scale, shift, w, b, conv=_conv_nobias):
+    """Eval forward with BatchNorm folded into w and b: relu(conv3x3(x) + b)."""
+    return relu_fwd(conv(bn_relu_on_load(x, scale, shift), w) + b)
+
+
+def dgrad_weights(w):
+    """The weights whose valid 3x3 correlation over the zero-padded dY is
+    conv_valid_bwd's dx: channels swapped, taps flipped."""
+    return np.ascontiguousarray(w.transpose(1, 0, 2, 3)[:, :, ::-1, ::-1])
+
+
+def site_d_pool(dypad, w, conv=_conv_nobias):
+    """Input gradient of a 3x3 conv from its padded dY (N,H+2,W+2,Co), w OIHW:
+    dx (N,H,W,Ci).  With a 2-pixel zero border it is conv_valid_bwd's dx."""
+    return conv(dypad, dgrad_weights(w))
+
+
+def relu_mask_bn(dx, yref, scale, shift, mean, invstd):
+    """dz' = dx where relu(bn(yref)) passed (yref * scale + shift > 0), and its
+    BatchNorm-backward sums."""
+    dz = dx * ((yref * scale + shift) > 0)
+    return dz, bn_bwd_sums(dz, yref, mean, invstd)
+
+
+def site_d_mask(dypad, w, yref, scale, shift, mean, invstd, conv=_conv_nobias):
+    """Input gradient into the producer's BatchNorm input: site_d_pool masked by
+    the producer's ReLU.  Returns dz', (sum dz', sum dz' * xhat)."""
+    return relu_mask_bn(site_d_pool(dypad, w, conv), yref, scale, shift, mean, invstd)
+
+
+def site_d_split(dypad, w, n_split, conv=_conv_nobias):
+    """Input gradient of an Up block's first conv, split at the concat: channels
+    < n_split (the skip's gradient), the rest (the upsampled tensor's gradient)
+    and the column sums of the rest (the ConvTranspose2d's bias gradient)."""
+    dx = site_d_pool(dypad, w, conv)
+    d1 = dx[..., n_split:]
+    return dx[..., :n_split], d1, d1.reshape(-1, d1.shape[-1]).sum(0)
+
+
+def site_t_fwd(x, w, b):
+    """ConvTranspose2d(k2, s2) forward (models/unet_model.py:45)."""
+    return convT2_fwd(x, w, b)
+
+
+def site_t_mask(dy, w, yref, scale, shift, mean, invstd):
+    """ConvTranspose2d input gradient, masked like site_d_mask.  dy (N,2H,2W,Co),
+    w (Ci,Co,2,2), yref (N,H,W,Ci)."""
+    n, h2, w2, _ = dy.shape
+    x0 = np.zeros((n, h2 // 2, w2 // 2, w.shape[0]), dy.dtype)
+    return relu_mask_bn(convT2_bwd(x0, w, dy)[0], yref, scale, shift, mean, invstd)
+
+
+# Winograd F(m x m, 3x3) as csrc/winograd.hip computes it: Y = A^T [(G g G^T) .
+# (B^T d B)] A per (m+2)^2 input patch.  The matrices are the kernels' (F2:
+# Lavin & Gray; F4: points 0, 1, -1, 2, -1/2, inf; F6: 0, +-1, +-2, +-1/2, inf),
+# written down as data; the arithmetic runs in `dtype`.
+WINOGRAD = {
+    2: dict(
+        BT=[[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]],
+        G=[[1, 0, 0], [1 / 2, 1 / 2, 1 / 2], [1 / 2, -1 / 2, 1 / 2], [0, 0, 1]],
+        AT=[[1, 1, 1, 0], [0, 1, -1, -1]]),
+    4: dict(
+        BT=[[1, 3 / 2, -2, -3 / 2, 1, 0], [0, -1, -5 / 2, -1 / 2, 1, 0], [0, 1, 1 / 2, -5 / 2, 1, 0],
+            [0, -1 / 2, -1, 1 / 2, 1, 0], [0, 2, -1, -2, 1, 0], [0, 1, 3 / 2, -2, -3 / 2, 1]],
+        G=[[1, 0, 0], [-1 / 3, -1 / 3, -1 / 3], [1 / 3, -1 / 3, 1 / 3], [1 / 15, 2 / 15, 4 / 15],
+           [-16 / 15, 8 / 15, -4 / 15], [0, 0, 1]],
+        AT=[[1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -1 / 2, 0], [0, 1, 1, 4, 1 / 4, 0], [0, 1, -1, 8, -1 / 8, 1]]),
+    6: dict(
+        BT=[[1, 0, -21 / 4, 0, 21 / 4, 0, -1, 0], [0, 1, 1, -17 / 4, -17 / 4, 1, 1, 0],
+            [0, -1, 1, 17 / 4, -17 / 4, -1, 1, 0], [0, 1 / 2, 1 / 4, -5 / 2, -5 / 4, 2, 1, 0],
+            [0, -1 / 2, 1 / 4, 5 / 2, -5 / 4, -2, 1, 0], [0, 2, 4, -5 / 2, -5, 1 / 2, 1, 0],
+            [0, -2, 4, 5 / 2, -5, -1 / 2, 1, 0], [0, -1, 0, 21 / 4, 0, -21 / 4, 0, 1]],
+        G=[[1, 0, 0], [-2 / 9, -2 / 9, -2 / 9], [-2 / 9, 2 / 9, -2 / 9], [1 / 90, 1 / 45, 2 / 45],
+           [1 / 90, -1 / 45, 2 / 45], [32 / 45, 16 / 45, 8 / 45], [32 / 45, -16 / 45, 8 / 45], [0, 0, 1]],
+        AT=[[1, 1, 1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 1 / 2, -1 / 2, 0], [0, 1, 1, 4, 4, 1 / 4, 1 / 4, 0],
+            [0, 1, -1, 8, -8, 1 / 8, -1 / 8, 0], [0, 1, 1, 16, 16, 1 / 16, 1 / 16, 0],
+            [0, 1, -1, 32, -32, 1 / 32, -1 / 32, 1]]),
+}
+
+
+def winograd_conv(x, w, m, dtype=np.float32):
+    """Valid 3x3 correlation (no bias) of x (N,H,W,Ci) with w (Co,Ci,3,3) by
+    Winograd F(m x m, 3x3), every operation in `dtype`; tiles that overhang the
+    output grid read zeros.  Returns (N,H-2,W-2,Co) in `dtype`."""
+    mats = WINOGRAD[m]
+    bt, g, at = (np.asarray(mats[k], dtype) for k in ("BT", "G", "AT"))
+    n, hh, ww, ci = x.shape
+    co = w.shape[0]
+    ho, wo = hh - 2, ww - 2
+    th, tw, a = -(-ho // m), -(-wo // m), m + 2
+    xp = np.zeros((n, th * m + 2, tw * m + 2, ci), dtype)
+    xp[:, :hh, :ww, :] = x
+    # d[i, j, n, ty, tx, c]: the (m+2)^2 patch of tile (ty, tx)
+    d = np.empty((a, a, n, th, tw, ci), dtype)
+    for i in range(a):
+        for j in range(a):
+            d[i, j] = xp[:, i:i + th * m:m, j:j + tw * m:m, :]
+    u = np.einsum("pi,ij...->pj...", bt, d)            # B^T d
+    u = np.einsum("qj,pj...->pq...", bt, u)            # (.) B
+    gw = np.asarray(w, dtype).transpose(2, 3, 1, 0)    # [ky][kx][ci][co]
+    v = np.einsum("pi,ij...->pj...", g, gw)
+    v = np.einsum("qj,pj...->pq...", g, v)             # G g G^T: [p][q][ci][co]
+    mm = np.matmul(u.reshape(a, a, n * th * tw, ci), v)  # the (m+2)^2 point GEMMs
+    y = np.einsum("ip,pq...->iq...", at, mm)
+    y = np.einsum("jq,iq...->ij...", at, y)            # A^T M A: [m][m][tiles][co]
+    y = y.reshape(m, m, n, th, tw, co).transpose(2, 3, 0, 4, 1, 5).reshape(n, th * m, tw * m, co)
+    assert y.dtype == np.dtype(dtype)
+    return np.ascontiguousarray(y[:, :ho, :wo, :])
+
+
+# ----------------------------------------------------------------------------
 # Whole network.
 # ----------------------------------------------------------------------------
 def output_size(h: int) -> int:

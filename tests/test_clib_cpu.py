@@ -213,3 +213,170 @@ def test_pipeline_crop_views_and_cpu_rejection():
         center_crop_views(t, (10, 3))
     with pytest.raises(ValueError):
         HeLaBatches(torch.zeros((2, 8, 8), dtype=torch.uint8), torch.zeros((2, 8, 8), dtype=torch.int32), 2, (4, 4))
+
+
+# ---------------------------------------------------------------------------
+# unet_gemm_site_* (the per-site GEMM entry point) and the igemm tile table:
+# the host-only paths
+# ---------------------------------------------------------------------------
+def _site_desc(L, site, prec="fp32", grid="main", **kw):
+    """A valid descriptor of a matrix case with stand-in pointers (never read:
+    the checks below run on the host)."""
+    from gemm_site_cases import Case
+
+    class Buf:
+        def __init__(self, *a, **k):
+            self.ptr = 0x1000
+
+    d = L.GemmSite()
+    Case(site, grid, prec, **kw).fill(d, lambda name: 0x1000, Buf)
+    return d
+
+
+def _igemm_ids_in_sources():
+    """Tile ids named in the sources' *_tile_rows() functions and igemm.hip's own rows."""
+    csrc = os.path.join(ROOT, "unet-segmentation_amd", "csrc")
+    ids = []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        text = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, f)).read())
+        blocks = re.findall(r"IgemmTileRows \w+_tile_rows\(\) \{(.*?)return tile_rows\(rows\);", text, flags=re.S)
+        blocks += re.findall(r"static const IgemmTile kF32Tiles\[\] = \{(.*?)\n\};", text, flags=re.S)
+        for b in blocks:
+            ids += [int(m) for m in re.findall(r"\b\w*tile\w*(?:<[^<>()]*>)?\((\d+)[,)]", b)]
+            ids += [int(m) for m in re.findall(r"\{(\d+), IgemmFamily::", b)]
+    return ids
+
+
+def test_igemm_tile_table_lists_the_rows_of_the_sources():
+    L = _lib()
+    table = L.igemm_tile_table()
+    ids = [t["id"] for t in table]
+    src = _igemm_ids_in_sources()
+    assert len(src) == len(set(src)) >= 60, src
+    assert sorted(ids) == sorted(src), set(ids) ^ set(src)
+    assert len(ids) == len(set(ids))
+    by = {t["id"]: t for t in table}
+    # a few rows read off the sources
+    assert by[4]["family"] == "Reg" and not by[4]["bf16"] and by[4]["ksplit"]
+    assert by[21]["bf16"] and by[21]["x3"] and by[36]["family"] == "Halo" and not by[36]["x3"]
+    assert [by[t]["wino_m"] for t in (70, 71, 74, 75, 76)] == [2, 4, 6, 2, 4] and not by[76]["ksplit"]
+    assert by[87]["family"] == "C64" and by[99]["family"] == "GemmRing" and by[86]["family"] == "Flat"
+    # a short buffer receives only what it holds
+    buf = (ctypes.c_int * 12)(*([-7] * 12))
+    assert L.load().unet_igemm_tile_table(buf, 1) == len(ids)
+    assert buf[0] == ids[0] and list(buf[6:]) == [-7] * 6
+
+
+def test_gemm_site_rejects_bad_descriptors():
+    import errno
+    L = _lib()
+    lib = L.load()
+    ok = _site_desc(L, "F_CAT")
+    assert lib.unet_gemm_site_check(ctypes.byref(ok), None) == 0
+    assert lib.unet_gemm_site_ws_bytes(ctypes.byref(ok)) > 0
+
+    def refused(name, **fields):
+        site = name
+        d = _site_desc(L, name)
+        for k, v in fields.items():
+            setattr(d, k, v)
+        assert lib.unet_gemm_site_check(ctypes.byref(d), None) == -errno.EINVAL, (site, fields)
+        assert lib.unet_gemm_site_ws_bytes(ctypes.byref(d)) == 0
+        # the run refuses it before it touches ws or the device
+        assert lib.unet_gemm_site_run(ctypes.byref(d), 0x1000, None) == -errno.EINVAL
+        assert "unet_gemm_site" in L.last_error()
+
+    refused("F_PLAIN", ci=124)             # channels per tap: a multiple of 8
+    refused("F_PLAIN", ci=4)
+    refused("F_PLAIN", co=100)             # columns: a multiple of 32
+    refused("D_POOL", co=20)
+    refused("T_FWD", co=12)
+    refused("F_CAT", c_split=60)
+    refused("F_CAT", c_split=128)          # nothing left for the second source
+    refused("F_CAT", oy=6)                 # the window leaves the stored skip grid
+    refused("F_CAT", ox=-1)
+    refused("D_SPLIT", n_split=48)         # a multiple of 32 ...
+    refused("D_SPLIT", n_split=0)
+    refused("D_SPLIT", n_split=192)        # ... inside the columns
+    for site, ptrs in (("F_PLAIN", ("src0", "wt", "dst0", "bias", "stats", "scale0")), ("F_CAT", ("src1",)),
+                       ("D_MASK", ("yref", "bn_scale", "bn_invstd", "bstats")), ("D_SPLIT", ("dst1", "colsum1")),
+                       ("T_FWD", ("bias",)), ("T_MASK", ("yref", "bn_mean"))):
+        for p in ptrs:
+            refused(site, **{p: None})     # scale0 alone: scale and shift come in pairs
+    refused("F_PLAIN", site=8)
+    refused("F_PLAIN", n=0)
+    assert lib.unet_gemm_site_check(None, None) == -errno.EINVAL
+    # ws: non-null, 256-byte aligned
+    assert lib.unet_gemm_site_run(ctypes.byref(ok), None, None) == -errno.EINVAL
+    assert lib.unet_gemm_site_run(ctypes.byref(ok), 0x1010, None) == -errno.EINVAL
+
+
+def test_gemm_site_strict_forcing_and_expected_map():
+    """op_strict: a forced tile or split that does not apply is -EINVAL (default:
+    the built-in tile in its place).  And the map of tests/gemm_site_cases.py --
+    which tile accepts which site on the main grid -- holds for every tile."""
+    import errno
+    from gemm_site_cases import SITES, PRECS, WINO_KNOBS, tiles_for, expected_sites
+    L = _lib()
+    lib = L.load()
+    table = L.igemm_tile_table()
+    knobs = dict(op_strict=0, op_precision=0, op_a16=0, igemm_variant=-1, wino_dgrad_max=4)
+    try:
+        d = _site_desc(L, "T_FWD")
+        d.tile = 52   # a 3x3 halo tile at a convT site
+        tile = ctypes.c_int(0)
+        assert lib.unet_gemm_site_check(ctypes.byref(d), ctypes.byref(tile)) == 0 and tile.value != 52
+        lib.unet_set_tuning(b"op_strict", 1)
+        assert lib.unet_gemm_site_check(ctypes.byref(d), None) == -errno.EINVAL
+        d.tile = 12345
+        assert lib.unet_gemm_site_check(ctypes.byref(d), None) == -errno.EINVAL
+        d.tile, d.split = 1, 3
+        assert lib.unet_gemm_site_check(ctypes.byref(d), ctypes.byref(tile)) == 0 and tile.value == 1
+        split_ws = lib.unet_gemm_site_ws_bytes(ctypes.byref(d))
+        d.split = 1
+        # the slab of an explicit K split lives in ws: 3 x M x N floats more
+        assert split_ws - lib.unet_gemm_site_ws_bytes(ctypes.byref(d)) == 3 * (2 * 13 * 19) * 256 * 4
+        d.split = 5   # 8 K chunks do not make 5 non-empty slices
+        assert lib.unet_gemm_site_check(ctypes.byref(d), None) == -errno.EINVAL
+        d = _site_desc(L, "F_PLAIN")
+        d.tile, d.split = 70, 3   # Winograd takes no K split
+        assert lib.unet_gemm_site_check(ctypes.byref(d), None) == -errno.EINVAL
+        # tile -1 = the igemm_variant knob; 0 = the built-in choice whatever the knob says
+        lib.unet_set_tuning(b"igemm_variant", 52)
+        d.tile, d.split = -1, 1
+        assert lib.unet_gemm_site_check(ctypes.byref(d), ctypes.byref(tile)) == 0 and tile.value == 52
+        d.tile = 0
+        assert lib.unet_gemm_site_check(ctypes.byref(d), ctypes.byref(tile)) == 0 and tile.value not in (52, -1)
+        lib.unet_set_tuning(b"igemm_variant", -1)
+        ran = set()
+        for prec, (p, a16) in PRECS.items():
+            lib.unet_set_tuning(b"op_precision", p)
+            lib.unet_set_tuning(b"op_a16", a16)
+            for t in table:
+                if t["id"] not in tiles_for(table, prec):
+                    continue
+                for k, v in WINO_KNOBS.get(t["id"], [{}])[0].items():
+                    lib.unet_set_tuning(k.encode(), v)
+                got = []
+                for site in SITES:
+                    d = _site_desc(L, site, prec)
+                    d.tile = t["id"]
+                    if lib.unet_gemm_site_check(ctypes.byref(d), ctypes.byref(tile)) == 0:
+                        assert tile.value == t["id"]
+                        got.append(site)
+                lib.unet_set_tuning(b"wino_dgrad_max", 4)
+                assert tuple(got) == expected_sites(t, prec), (prec, t["id"], t["family"], got)
+                if got:
+                    ran.add(t["id"])
+        # the tiles no site of the main matrix takes have a case of their own
+        assert {t["id"] for t in table} - ran == {86, 87}
+        lib.unet_set_tuning(b"op_precision", 1)
+        lib.unet_set_tuning(b"op_a16", 1)
+        d = _site_desc(L, "F_PLAIN", "bf16", cg=64, cols=64)
+        d.tile = 87
+        assert lib.unet_gemm_site_check(ctypes.byref(d), None) == 0
+    finally:
+        for k, v in knobs.items():
+            lib.unet_set_tuning(k.encode(), v)

@@ -80,83 +80,14 @@ def lib():
     return _lib.load()
 
 
-GUARD = 256      # bytes on either side; keeps the slice 256-byte aligned
-PATTERN = 0xA5
-_KEEP = []
-_GUARDED = []
-_NP2T = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
-         np.dtype(np.int64): torch.int64, np.dtype(np.uint8): torch.uint8}
-
-
-class G:
-    """A device buffer of exactly `shape` x dtype inside a larger allocation:
-    [guard | payload | guard].  The payload starts as 0xFF bytes (NaN for fp32 /
-    fp64, all-ones for integers) unless `init` gives its contents."""
-
-    def __init__(self, shape, dtype=np.float32, init=None, output=True):
-        shape = (shape,) if np.isscalar(shape) else tuple(shape)
-        self.dtype = np.dtype(dtype)
-        self.nbytes = int(np.prod(shape, dtype=np.int64)) * self.dtype.itemsize
-        self.raw = torch.full((GUARD + self.nbytes + GUARD,), PATTERN, dtype=torch.uint8, device="cuda")
-        assert self.raw.data_ptr() % 256 == 0
-        self.bytes = self.raw[GUARD:GUARD + self.nbytes]
-        self.bytes.fill_(0xFF)
-        self.t = self.bytes.view(_NP2T[self.dtype]).view(shape)
-        if init is not None:
-            self.t.copy_(torch.from_numpy(np.ascontiguousarray(init, dtype=self.dtype)))
-        # a float output must end up finite everywhere: it was written
-        self.output = output and self.dtype.kind == "f"
-        _GUARDED.append(self)
-
-    @property
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def np(self):
-        return self.t.cpu().numpy()
-
-    def f64(self):
-        return self.np().astype(np.float64)
-
-    def check(self):
-        for name, g in (("front", self.raw[:GUARD]), ("back", self.raw[GUARD + self.nbytes:])):
-            bad = (g != PATTERN).nonzero().flatten().cpu().numpy()
-            assert bad.size == 0, f"{name} guard of a {self.nbytes}-byte buffer overwritten at bytes {bad[:8]}"
-        if self.output:
-            a = self.np()
-            assert np.isfinite(a).all(), f"{int((~np.isfinite(a)).sum())} of {a.size} output elements not written"
-
-
-def ws_buf(nbytes):
-    """Workspace of exactly nbytes (0xFF-filled, guarded)."""
-    return G(int(nbytes), np.uint8)
-
-
-def done():
-    """Synchronise, then check every guarded buffer of this test."""
-    torch.cuda.synchronize()
-    for g in _GUARDED:
-        g.check()
-    _GUARDED.clear()
-
-
-def dev(a, dtype=torch.float32):
-    t = torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dtype)
-    _KEEP.append(t)
-    return t
+from guarded import G, ws_buf, done, dev, stream, begin, release, _KEEP  # noqa: E402  (the guarded buffers, shared)
 
 
 @pytest.fixture(autouse=True)
 def _release():
-    _GUARDED.clear()
+    begin()
     yield
-    torch.cuda.synchronize()
-    _KEEP.clear()
-    _GUARDED.clear()
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    release()
 
 
 def rel_err(a, b):

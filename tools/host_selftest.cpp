@@ -627,8 +627,83 @@ static void test_selection(const char* golden, bool record) {
   CHECK(bad == 0);
 }
 
+// unet_gemm_site_*: the descriptor's validation, the strict knob and the tile
+// table's export (host only: nothing is launched, no pointer is read)
+static void test_gemm_site() {
+  float* const p = reinterpret_cast<float*>(uintptr_t{4096});
+  double* const q = reinterpret_cast<double*>(uintptr_t{4096});
+  auto base = [&](int site) {
+    unet_gemm_site d{};
+    d.site = site;
+    d.n = 2, d.h = 13, d.w = 19, d.ci = 128, d.co = 128;
+    d.tile = 0, d.split = 1;
+    d.src0 = d.wt = d.bias = d.scale0 = d.shift0 = p;
+    d.dst0 = p;
+    d.stats = q;
+    return d;
+  };
+  unet_gemm_site d = base(UNET_SITE_F_PLAIN);
+  int tile = 0;
+  CHECK(unet_gemm_site_check(&d, &tile) == 0 && tile > 0);
+  const size_t ws1 = unet_gemm_site_ws_bytes(&d);
+  CHECK(ws1 >= 2 * sizeof(float) * 9 * 128 * 128 && ws1 % 256 == 0);
+  d.tile = 1, d.split = 3;  // the slab of an explicit K split lives in ws
+  CHECK(unet_gemm_site_check(&d, &tile) == 0 && tile == 1);
+  CHECK(unet_gemm_site_ws_bytes(&d) == ws1 + sizeof(float) * 3 * (2 * 13 * 19) * 128);
+  d = base(UNET_SITE_F_PLAIN);
+  d.ci = 124;
+  CHECK(unet_gemm_site_check(&d, nullptr) == -EINVAL && unet_gemm_site_ws_bytes(&d) == 0);
+  CHECK(std::strstr(unet_last_error(), "unet_gemm_site") != nullptr);
+  d = base(UNET_SITE_F_PLAIN);
+  d.co = 100;
+  CHECK(unet_gemm_site_check(&d, nullptr) == -EINVAL);
+  d = base(UNET_SITE_F_PLAIN);
+  d.stats = nullptr;
+  CHECK(unet_gemm_site_check(&d, nullptr) == -EINVAL);
+  CHECK(unet_gemm_site_run(&d, p, nullptr) == -EINVAL);  // before anything is launched
+  d = base(UNET_SITE_F_PLAIN);
+  CHECK(unet_gemm_site_run(&d, nullptr, nullptr) == -EINVAL);
+  CHECK(unet_gemm_site_run(&d, reinterpret_cast<void*>(uintptr_t{4100}), nullptr) == -EINVAL);  // ws alignment
+  d = base(UNET_SITE_D_SPLIT);
+  d.ci = 192, d.scale0 = d.shift0 = nullptr, d.dst1 = p, d.colsum1 = q;
+  d.n_split = 48;
+  CHECK(unet_gemm_site_check(&d, nullptr) == -EINVAL);
+  d.n_split = 64;
+  CHECK(unet_gemm_site_check(&d, &tile) == 0);
+  d.colsum1 = nullptr;
+  CHECK(unet_gemm_site_check(&d, nullptr) == -EINVAL);
+  d = base(UNET_SITE_F_CAT);
+  d.src1 = p, d.c_split = 64, d.skip_h = 20, d.skip_w = 25, d.oy = 2, d.ox = 3;
+  CHECK(unet_gemm_site_check(&d, nullptr) == 0);
+  d.ox = 5;  // the window leaves the stored grid
+  CHECK(unet_gemm_site_check(&d, nullptr) == -EINVAL);
+  CHECK(unet_gemm_site_check(nullptr, nullptr) == -EINVAL);
+  // strict forcing: a 3x3 halo tile at a convT site
+  d = base(UNET_SITE_T_FWD);
+  d.co = 64, d.scale0 = d.shift0 = nullptr, d.tile = 52;
+  CHECK(unet_gemm_site_check(&d, &tile) == 0 && tile != 52);  // default: the built-in tile in its place
+  CHECK(unet_set_tuning("op_strict", 1) == 0);
+  CHECK(unet_gemm_site_check(&d, nullptr) == -EINVAL);
+  d.tile = 4;
+  CHECK(unet_gemm_site_check(&d, &tile) == 0 && tile == 4);
+  d.split = 5;  // 8 chunks of K do not make 5 slices
+  CHECK(unet_gemm_site_check(&d, nullptr) == -EINVAL);
+  CHECK(unet_set_tuning("op_strict", 0) == 0);
+  // the tile table's export agrees with the table
+  const int n = unet_igemm_tile_table(nullptr, 0);
+  CHECK(n == (int)unet::igemm_tiles().size() && n > 60);
+  std::vector<int> rows(6 * (size_t)n, -1);
+  CHECK(unet_igemm_tile_table(rows.data(), n) == n);
+  for (int i = 0; i < n; ++i) {
+    const unet::IgemmTile* t = unet::igemm_tile(rows[6 * i]);
+    CHECK(t != nullptr && (int)t->family == rows[6 * i + 1] && t->bf16 == (rows[6 * i + 2] != 0) &&
+          t->x3 == (rows[6 * i + 3] != 0) && t->ksplit == (rows[6 * i + 4] != 0) && t->wino_m == rows[6 * i + 5]);
+  }
+}
+
 int main(int argc, char** argv) {
   test_plans();
+  test_gemm_site();
   test_lsap();
   test_tracker();
   test_ctc();

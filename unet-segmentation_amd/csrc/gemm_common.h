@@ -275,6 +275,7 @@ __device__ __forceinline__ void epi_fast(const Epilogue& e, const floatx16 (&acc
         if constexpr (H16) {
           bits = bf16_of(v);
           if constexpr (KIND == 1 || KIND == 2) v = __uint_as_float(bits << 16);  // statistics of the stored value
+          else if (csum) v = __uint_as_float(bits << 16);  // ... and the column sums of a bf16 second destination
         }
         if constexpr (KIND == 2) {
           const bool on = fmaf(yv[r], bsc, bsh) > 0.f;
@@ -603,9 +604,10 @@ __device__ __forceinline__ void igemm_finish(const IgemmArgs& args, floatx16 (&a
             if (k >= lim) continue;
             const unsigned idx = ib + (unsigned)(k * dC);
             float v = acc[i][j][r] + bias;
-            // a bf16-stored conv output / BN-input gradient: the statistics are
-            // those of the rounded values its consumers read
-            if (dh16 && (e.stats || bwd_mask)) v = round_bf(v);
+            // a bf16-stored conv output / BN-input gradient: the statistics (and
+            // the second destination's column sums) are those of the rounded
+            // values its consumers read
+            if (dh16 && (e.stats || bwd_mask || (second && e.colsum1))) v = round_bf(v);
             if (bwd_mask) {
               v = (fmaf(yv[r], bsc, bsh) > 0.f) ? v : 0.f;
               s1[j] += v;
@@ -650,7 +652,7 @@ __device__ __forceinline__ void igemm_finish(const IgemmArgs& args, floatx16 (&a
         float v = acc[i][j][r] + bias;
         // a bf16-stored conv output: its BatchNorm statistics are those of the
         // rounded values the consumers will normalise
-        if (d.h16 && (e.stats || bwd_mask)) v = round_bf(v);
+        if (d.h16 && (e.stats || bwd_mask || (second && e.colsum1))) v = round_bf(v);
         size_t idx;
         if (linear) {
           idx = (size_t)m * d.C + dcol;

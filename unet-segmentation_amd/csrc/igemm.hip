@@ -862,7 +862,7 @@ __global__ __launch_bounds__(256) void k_splitk_epi(const IgemmArgs args) {
       }
     }
     float vv[4] = {v.x, v.y, v.z, v.w};
-    if (d.h16 && (e.stats || bwd_mask)) {  // bf16-stored output: statistics of the rounded values
+    if (d.h16 && (e.stats || bwd_mask || (second && e.colsum1))) {  // bf16-stored output: statistics of the rounded values
 #pragma unroll
       for (int q = 0; q < 4; ++q) vv[q] = round_bf(vv[q]);
     }

@@ -31,6 +31,31 @@ int g_op_prec = UNET_PREC_FP32;
 // bf16 before its BN+ReLU transform, the input gradient stores the padded dY
 // bf16.  Lets op-level tests and tools run the plan's exact GEMM configuration.
 int g_op_a16 = 0;
+// unet_set_tuning("op_strict", 1): a forced tile ("igemm_variant" > 0, or a
+// unet_gemm_site descriptor's tile / split) that does not apply to a per-op
+// call is -EINVAL before anything is launched, instead of the built-in tile
+// running in its place (tests: the only way to know which tile ran)
+int g_op_strict = 0;
+
+// the K-chunk quantum launch_igemm holds a call with forced tile t to
+int op_quantum(const IgemmTile* t) { return t && t->family == IgemmFamily::WinoFused && t->wino_m == 2 ? 8 : 16; }
+// a as the GEMM will see it: packed B in op_precision's planes (pointers only)
+IgemmArgs op_as_launched(IgemmArgs a) {
+  if (g_op_prec != UNET_PREC_FP32 && a.b) {
+    a.bh = reinterpret_cast<const uint16_t*>(a.b);
+    a.bl = g_op_prec == UNET_PREC_BF16X3 ? a.bh : nullptr;
+    a.b = nullptr;
+  }
+  return a;
+}
+// tile `id` applies to the call: its fits() and launch_igemm's channel quantum
+bool op_tile_applies(const IgemmArgs& a0, int id) {
+  const IgemmArgs a = op_as_launched(a0);
+  const int q = op_quantum(igemm_tile(id));
+  return igemm_tile_fits(a, id) && a.K % q == 0 && a.a.Cg % q == 0 && a.a.c_split % q == 0;
+}
+// op_strict: false when "igemm_variant" forces a tile that does not apply to a
+bool op_forced_ok(const IgemmArgs& a) { return !g_op_strict || g_tune_igemm <= 0 || op_tile_applies(a, g_tune_igemm); }
 
 // bf16 / split per-op GEMMs: round the packed fp32 B (n elements) into
 // `scratch` (4n bytes: hi plane, then the lo plane of split operands) and point
@@ -134,7 +159,6 @@ int unet_conv3x3_fwd(const float* x, int n, int h, int w, int ci, const float* w
   if (ci % 16 && (g_op_prec != UNET_PREC_FP32 || g_tune_igemm <= 0)) return -EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(st);
   float* wf = reinterpret_cast<float*>(ws);
-  OPCK(launch_pack_conv(wt, co, ci, 3, 3, wf, nullptr, s));
   IgemmArgs a;
   Src x0;
   x0.ptr = x;
@@ -143,12 +167,12 @@ int unet_conv3x3_fwd(const float* x, int n, int h, int w, int ci, const float* w
   x0.C = ci;
   x0.scale = xs;
   x0.shift = xb;
+  uint16_t* x16 = nullptr;
   if (g_op_prec == UNET_PREC_BF16 && g_op_a16) {
     const size_t wb = al256(sizeof(float) * 9 * (size_t)ci * co);
     const size_t off = 2 * wb + al256(sizeof(float) * (size_t)n * (h + 2) * (w + 2) * co) +
                        al256(sizeof(float) * 4 * co) + al256(sizeof(double) * kStatGroups * 2 * co);
-    uint16_t* x16 = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(ws) + off);
-    OPCK(launch_f2bf(x, x16, (size_t)n * h * w * ci, s));
+    x16 = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(ws) + off);
     x0.ptr = reinterpret_cast<const float*>(x16);
     x0.h16 = 1;
   }
@@ -166,6 +190,9 @@ int unet_conv3x3_fwd(const float* x, int n, int h, int w, int ci, const float* w
   a.e.d[0] = Dst{y, h - 2, w - 2, co, 0, 0};
   op_set_wino(a, ws, n, h, w, ci, co);
   if (ci % 16 && resolve_forced_igemm(a, g_tune_igemm).tile < 0) return -EINVAL;
+  if (!op_forced_ok(a)) return -EINVAL;
+  OPCK(launch_pack_conv(wt, co, ci, 3, 3, wf, nullptr, s));
+  if (x16) OPCK(launch_f2bf(x, x16, (size_t)n * h * w * ci, s));
   OPCK(op_b_to_bf16(a, 9 * (size_t)ci * co, reinterpret_cast<char*>(ws) + al256(sizeof(float) * 9 * (size_t)ci * co),
                     s));
   OPCK(launch_igemm(a, s));
@@ -183,12 +210,7 @@ int unet_conv3x3_dgrad(const float* dy, int n, int h, int w, int ci, const float
   float* wd = reinterpret_cast<float*>(p + wb);
   float* dyp = reinterpret_cast<float*>(p + 2 * wb);
   float* coef = reinterpret_cast<float*>(p + 2 * wb + al256(sizeof(float) * (size_t)n * (h + 2) * (w + 2) * co));
-  OPCK(launch_pack_conv(wt, co, ci, 3, 3, wf, wd, s));
-  // zero-bordered copy of dy: dYpad = 1*dy + 0*(y-0) + 0
-  OPCK(launch_fill(coef, co, 1.f, s));
-  OPCK(launch_fill(coef + co, 3 * (size_t)co, 0.f, s));
   const int dy16 = g_op_prec == UNET_PREC_BF16 && g_op_a16;
-  OPCK(launch_bnb_apply(dy, dy, coef, n, h - 2, w - 2, co, dyp, 2, s, dy16, 0));
   IgemmArgs a;
   Src d;
   d.ptr = dyp;
@@ -209,6 +231,12 @@ int unet_conv3x3_dgrad(const float* dy, int n, int h, int w, int ci, const float
   a.e.d[0] = Dst{dx, h, w, ci, 0, 0};
   op_set_wino(a, ws, n, h, w, ci, co);
   if (co % 16 && resolve_forced_igemm(a, g_tune_igemm).tile < 0) return -EINVAL;
+  if (!op_forced_ok(a)) return -EINVAL;
+  OPCK(launch_pack_conv(wt, co, ci, 3, 3, wf, wd, s));
+  // zero-bordered copy of dy: dYpad = 1*dy + 0*(y-0) + 0
+  OPCK(launch_fill(coef, co, 1.f, s));
+  OPCK(launch_fill(coef + co, 3 * (size_t)co, 0.f, s));
+  OPCK(launch_bnb_apply(dy, dy, coef, n, h - 2, w - 2, co, dyp, 2, s, dy16, 0));
   OPCK(op_b_to_bf16(a, 9 * (size_t)ci * co, wf, s));
   OPCK(launch_igemm(a, s));
   return 0;
@@ -297,7 +325,6 @@ int unet_convT2_fwd(const float* x, int n, int h, int w, int ci, const float* wt
   char* p = reinterpret_cast<char*>(ws);
   float* wf = reinterpret_cast<float*>(p);
   float* wd = reinterpret_cast<float*>(p + al256(sizeof(float) * 4 * (size_t)ci * co));
-  OPCK(launch_pack_convT(wt, ci, co, wf, wd, s));
   IgemmArgs a;
   Src x0;
   x0.ptr = x;
@@ -316,6 +343,8 @@ int unet_convT2_fwd(const float* x, int n, int h, int w, int ci, const float* wt
   a.e.bias = bias;
   a.e.shuffle_co = co;
   a.e.d[0] = Dst{y, 2 * h, 2 * w, co, 0, 0};
+  if (!op_forced_ok(a)) return -EINVAL;
+  OPCK(launch_pack_convT(wt, ci, co, wf, wd, s));
   OPCK(op_b_to_bf16(a, 4 * (size_t)ci * co, p + 2 * al256(sizeof(float) * 4 * (size_t)ci * co), s));
   OPCK(launch_igemm(a, s));
   return 0;
@@ -331,7 +360,6 @@ int unet_convT2_bwd(const float* x, const float* dy, int n, int h, int w, int ci
   float* wd = reinterpret_cast<float*>(p + wb);
   float* dwp = reinterpret_cast<float*>(p + 2 * wb);
   double* st2 = reinterpret_cast<double*>(p + 3 * wb);
-  OPCK(launch_pack_convT(wt, ci, co, wf, wd, s));
   Src d;
   d.ptr = dy;
   d.H = 2 * h;
@@ -350,6 +378,8 @@ int unet_convT2_bwd(const float* x, const float* dy, int n, int h, int w, int ci
   a.N = ci;
   a.K = 4 * co;
   a.e.d[0] = Dst{dx, h, w, ci, 0, 0};
+  if (!op_forced_ok(a)) return -EINVAL;
+  OPCK(launch_pack_convT(wt, ci, co, wf, wd, s));
   OPCK(op_b_to_bf16(a, 4 * (size_t)ci * co, wf, s));  // wf (4n bytes) is not read again
   OPCK(launch_igemm(a, s));
   OPCK(hipMemsetAsync(dwp, 0, sizeof(float) * 4 * (size_t)ci * co, s));
@@ -591,6 +621,7 @@ int unet_set_tuning(const char* key, int value) {
   else if (k == "wino4_fwd_min_cg") g_wino4_fwd_min_cg = value;
   else if (k == "wino4_fwd_small_cg") g_wino4_fwd_small_cg = value;
   else if (k == "op_a16") g_op_a16 = value != 0;
+  else if (k == "op_strict") g_op_strict = value != 0;
   else if (k == "maxpool_vec8") g_maxpool_vec8 = value;
   else if (k == "bnb_fuse") g_bnb_fuse = value;
   else if (k == "wgrad_early_u") g_wgrad_early_u = value;
@@ -758,6 +789,302 @@ int unet_tile_warp(const uint8_t* frames, const uint16_t* labels, const float* w
 int unet_mask_from_logits(const float* logits, uint8_t* mask, int n, int h, int w, unet_stream_t st) {
   OPCK(launch_mask(logits, mask, n, h, w, reinterpret_cast<hipStream_t>(st)));
   return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// unet_gemm_site: one forward / input-gradient GEMM with the arguments the plan
+// builds at that launch site (plan.hip run_forward / run_backward), on caller
+// buffers.  Layout of ws (256-B aligned pieces): packed B (forward form, then
+// the input-gradient form), its bf16 planes, the bf16 copies of the sources and
+// of yref (op_a16), the split-K / stream-K slab, the Winograd scratch.
+// ---------------------------------------------------------------------------
+namespace {
+struct SiteBuild {
+  IgemmArgs a;
+  GemmChoice c;          // tile < 0: the built-in choice
+  float *wf, *wd;        // packed B of the forward / the input-gradient GEMM
+  uint16_t* b16;         // bf16 planes of the GEMM's B (nullptr: fp32)
+  size_t nw;             // weight elements
+  uint16_t *s16[2], *y16;  // bf16 copies (nullptr: none)
+  size_t ns[2], ny;      // their element counts
+  size_t bytes;
+  int nstat, ncs;        // columns of stats / bstats and of colsum1
+};
+
+bool site_is_fwd(int s) { return s == UNET_SITE_F_PLAIN || s == UNET_SITE_F_CAT || s == UNET_SITE_F_EVAL; }
+bool site_is_dgrad(int s) { return s == UNET_SITE_D_POOL || s == UNET_SITE_D_MASK || s == UNET_SITE_D_SPLIT; }
+bool site_masks(int s) { return s == UNET_SITE_D_MASK || s == UNET_SITE_T_MASK; }
+
+// the built-in choice, whatever "igemm_variant" says
+int site_builtin_tile(const IgemmArgs& a) {
+  const int knob = g_tune_igemm;
+  g_tune_igemm = -1;
+  const int t = igemm_heuristic_tile(a);
+  g_tune_igemm = knob;
+  return t;
+}
+
+// the K slices launch_igemm_v makes of a request for `split` with tile t
+int site_slices(const IgemmArgs& a, const IgemmTile& t, int split) {
+  const int nk = a.K / t.bk;
+  int ks = split < 1 || t.wino_m ? 1 : (split > nk ? nk : split);
+  if (ks > 1) {
+    const int per = (nk + ks - 1) / ks;
+    ks = (nk + per - 1) / per;
+  }
+  return ks;
+}
+
+// Validates d and lays the GEMM out over ws (pointers only, nothing is
+// launched; ws may be any non-null address when only the layout is wanted).
+// 0, or -EINVAL with the reason in unet_last_error().
+int site_build(const unet_gemm_site* dp, char* ws, SiteBuild& b) {
+  auto bad = [](const char* why) {
+    set_last_error(std::string("unet_gemm_site: ") + why);
+    return -EINVAL;
+  };
+  if (!dp) return bad("null descriptor");
+  const unet_gemm_site& d = *dp;
+  if (d.site < UNET_SITE_F_PLAIN || d.site > UNET_SITE_T_MASK) return bad("unknown site");
+  if (d.n < 1 || d.h < 1 || d.w < 1 || d.ci < 8 || d.co < 8) return bad("need n, h, w >= 1 and ci, co >= 8");
+  if ((long long)d.n * (d.h + 2) * (d.w + 2) * 4 > 0x7fffffffLL) return bad("grid too large");
+  const bool fwd = site_is_fwd(d.site), dgrad = site_is_dgrad(d.site), cat = d.site == UNET_SITE_F_CAT;
+  const bool tfwd = d.site == UNET_SITE_T_FWD, tmask = d.site == UNET_SITE_T_MASK, split2 = d.site == UNET_SITE_D_SPLIT;
+  const int Cg = fwd || tfwd ? d.ci : d.co;                // channels per tap
+  const int N = fwd ? d.co : tfwd ? 4 * d.co : d.ci;       // GEMM columns
+  if (Cg % 8 || N % 32) return bad("channels per tap must be a multiple of 8, columns a multiple of 32");
+  if (tfwd && d.co % 8) return bad("convT co must be a multiple of 8");
+  if (cat && (d.c_split < 8 || d.c_split >= d.ci || d.c_split % 8)) return bad("c_split must be a multiple of 8 in (0, ci)");
+  if (cat && (d.oy < 0 || d.ox < 0 || d.oy + d.h + 2 > d.skip_h || d.ox + d.w + 2 > d.skip_w))
+    return bad("the cropped window leaves the stored skip grid");
+  if (split2 && (d.n_split < 32 || d.n_split >= N || d.n_split % 32)) return bad("n_split must be a multiple of 32 in (0, ci)");
+  if (!d.src0 || !d.wt || !d.dst0) return bad("null src0 / wt / dst0");
+  if (cat && !d.src1) return bad("F_CAT needs src1");
+  if ((d.scale0 == nullptr) != (d.shift0 == nullptr) || (d.scale1 == nullptr) != (d.shift1 == nullptr))
+    return bad("scale and shift come in pairs");
+  if ((dgrad || tmask) && (d.scale0 || d.scale1)) return bad("input-gradient sources take no transform");
+  if (site_masks(d.site) && (!d.yref || !d.bn_scale || !d.bn_shift || !d.bn_mean || !d.bn_invstd || !d.bstats))
+    return bad("mask sites need yref, bn_scale / shift / mean / invstd and bstats");
+  if (split2 && (!d.dst1 || !d.colsum1)) return bad("D_SPLIT needs dst1 and colsum1");
+  if ((d.site == UNET_SITE_F_PLAIN || cat) && !d.stats) return bad("F_PLAIN / F_CAT need stats");
+  if ((fwd || tfwd) && !d.bias) return bad("forward sites need bias");
+
+  const int h16 = g_op_prec == UNET_PREC_BF16 && g_op_a16;
+  b = SiteBuild{};
+  const bool conv = fwd || dgrad;
+  b.nw = (size_t)(conv ? 9 : 4) * d.ci * d.co;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* p = ws + off;
+    off += al256(bytes);
+    return p;
+  };
+  b.wf = reinterpret_cast<float*>(take(sizeof(float) * b.nw));
+  b.wd = reinterpret_cast<float*>(take(sizeof(float) * b.nw));
+  b.b16 = g_op_prec != UNET_PREC_FP32 ? reinterpret_cast<uint16_t*>(take(sizeof(float) * b.nw)) : nullptr;
+
+  IgemmArgs& a = b.a;
+  Gather& g = a.a;
+  g.Cg = g.c_split = Cg;
+  g.Hg = d.h;
+  g.Wg = d.w;
+  g.nimg = d.n;
+  Src s0;
+  s0.ptr = d.src0;
+  s0.C = Cg;
+  s0.scale = d.scale0;
+  s0.shift = d.shift0;
+  if (conv) {
+    g.taps_h = g.taps_w = 3;
+    s0.H = d.h + 2;
+    s0.W = d.w + 2;
+  } else if (tmask) {
+    g.taps_h = g.taps_w = 2;
+    g.stride = 2;
+    s0.H = 2 * d.h;
+    s0.W = 2 * d.w;
+  } else {
+    s0.H = d.h;
+    s0.W = d.w;
+  }
+  g.s[0] = g.s[1] = s0;
+  if (cat) {  // input_gather, l >= 10: cat([crop(skip), up], 1) without a copy
+    g.s[0].H = d.skip_h;
+    g.s[0].W = d.skip_w;
+    g.s[0].C = d.c_split;
+    g.s[0].oy = d.oy;
+    g.s[0].ox = d.ox;
+    g.s[1].ptr = d.src1;
+    g.s[1].C = d.ci - d.c_split;
+    g.s[1].scale = d.scale1;
+    g.s[1].shift = d.shift1;
+    g.c_split = d.c_split;
+  }
+  for (int k = 0; k < (cat ? 2 : 1); ++k) {
+    b.ns[k] = (size_t)d.n * g.s[k].H * g.s[k].W * g.s[k].C;
+    if (h16) {
+      b.s16[k] = reinterpret_cast<uint16_t*>(take(sizeof(uint16_t) * b.ns[k]));
+      g.s[k].ptr = reinterpret_cast<const float*>(b.s16[k]);
+      g.s[k].h16 = 1;
+    }
+  }
+  if (!cat) g.s[1] = g.s[0];
+  a.M = d.n * d.h * d.w;
+  a.N = N;
+  a.K = g.taps_h * g.taps_w * Cg;
+  a.b = fwd || tfwd ? b.wf : b.wd;
+  a.fwd = fwd;
+  Epilogue& e = a.e;
+  e.bias = fwd || tfwd ? d.bias : nullptr;
+  e.d[0] = Dst{reinterpret_cast<float*>(d.dst0), d.h, d.w, N, 0, 0, h16};
+  if (tfwd) {
+    e.shuffle_co = d.co;
+    e.d[0] = Dst{reinterpret_cast<float*>(d.dst0), 2 * d.h, 2 * d.w, d.co, 0, 0, h16};
+  }
+  b.nstat = N;
+  if (split2) {
+    e.n_split = d.n_split;
+    e.d[0].C = d.n_split;
+    e.d[1] = Dst{reinterpret_cast<float*>(d.dst1), d.h, d.w, N - d.n_split, 0, 0, h16};
+    e.colsum1 = d.colsum1;
+    b.ncs = N - d.n_split;
+  }
+  if (d.site == UNET_SITE_F_PLAIN || cat) e.stats = d.stats;
+  if (d.site == UNET_SITE_F_EVAL) e.relu = 1;
+  if (site_masks(d.site)) {
+    e.yref = d.yref;
+    b.ny = (size_t)a.M * N;
+    if (h16) {
+      b.y16 = reinterpret_cast<uint16_t*>(take(sizeof(uint16_t) * b.ny));
+      e.yref = reinterpret_cast<const float*>(b.y16);
+      e.yref_h16 = 1;
+    }
+    e.bn_scale = d.bn_scale;
+    e.bn_shift = d.bn_shift;
+    e.bn_mean = d.bn_mean;
+    e.bn_invstd = d.bn_invstd;
+    e.bstats = d.bstats;
+  }
+  if (b.b16) {
+    a.bh = b.b16;
+    a.bl = g_op_prec == UNET_PREC_BF16X3 ? b.b16 + b.nw : nullptr;
+    a.b = nullptr;
+  }
+
+  // the variant: the descriptor's tile, else the knob's, else the built-in one
+  const int want = d.tile > 0 ? d.tile : (d.tile == -1 && g_tune_igemm > 0 ? g_tune_igemm : -1);
+  const IgemmTile* t = want > 0 ? igemm_tile(want) : nullptr;
+  if (want > 0 && !t && g_op_strict) return bad("no such tile");
+  // the scratch a Winograd tile works in (sized like the plan's: the unfused
+  // tiles' U / M / V, or the fused tiles' transformed weights + claim counters)
+  if (t && t->wino_m && conv) {
+    a.wino_ws_bytes = std::max(al256(wino_ws_bytes_grid(d.n, d.h, d.w, Cg, N)), al256(sizeof(float) * 36 * (size_t)Cg * N) + 256);
+    a.wino_ws = reinterpret_cast<float*>(ws + off);  // taken below, after the slab
+  }
+  if (d.split > 1 || (t && t->slab_bytes)) a.slab = reinterpret_cast<float*>(ws + off);  // taken below, if used
+  const int q = op_quantum(t);
+  const bool chunks_ok = a.K % q == 0 && Cg % q == 0 && g.c_split % q == 0;
+  if (t && !(chunks_ok && igemm_tile_fits(a, t->id))) {
+    if (g_op_strict) return bad("the forced tile does not apply to this site (its fits() refuses the arguments)");
+    t = nullptr;  // the built-in tile in its place
+  }
+  int ks = 1;
+  if (d.split > 1) {  // of the forced tile, else of the built-in one
+    const IgemmTile* st = t ? t : igemm_tile(chunks_ok ? site_builtin_tile(a) : -1);
+    if (st && st->ksplit && N % 64 == 0 && a.K % st->bk == 0) ks = site_slices(a, *st, d.split);
+    if (g_op_strict && ks != d.split)
+      return bad("the K split does not apply to the tile (no split-K form, or its K chunks do not divide that way)");
+    if (ks > 1) t = st;
+  }
+  if (!t && (!chunks_ok || site_builtin_tile(a) < 0)) return bad("no built-in tile takes these channel counts");
+  b.c = t ? GemmChoice{t->id, ks} : GemmChoice{};
+  size_t slab = ks > 1 ? igemm_slab_bytes(a, ks) : 0;
+  if (t && t->slab_bytes && ks == 1) slab = t->slab_bytes(a);
+  if (slab == ~(size_t)0) slab = 0;
+  a.slab = slab ? reinterpret_cast<float*>(take(slab)) : nullptr;
+  if (a.wino_ws) {
+    a.wino_ws = reinterpret_cast<float*>(ws + off);
+    take(a.wino_ws_bytes);
+  }
+  // a tile that wants its slab or scratch sees them only now
+  if (t && !igemm_tile_fits(a, t->id)) {
+    if (g_op_strict) return bad("the forced tile does not apply to this site (its fits() refuses the arguments)");
+    b.c = GemmChoice{};
+  }
+  b.bytes = off;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int unet_gemm_site_check(const unet_gemm_site* d, int* tile) {
+  SiteBuild b;
+  const int r = site_build(d, reinterpret_cast<char*>(uintptr_t{4096}), b);
+  if (r) return r;
+  if (tile) *tile = b.c.tile > 0 ? b.c.tile : site_builtin_tile(b.a);
+  return 0;
+}
+
+size_t unet_gemm_site_ws_bytes(const unet_gemm_site* d) {
+  SiteBuild b;
+  return site_build(d, reinterpret_cast<char*>(uintptr_t{4096}), b) ? 0 : b.bytes;
+}
+
+int unet_gemm_site_run(const unet_gemm_site* d, void* ws, unet_stream_t st) {
+  if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255)) {
+    set_last_error("unet_gemm_site_run: ws must be 256-byte aligned and hold unet_gemm_site_ws_bytes");
+    return -EINVAL;
+  }
+  SiteBuild b;
+  if (const int r = site_build(d, reinterpret_cast<char*>(ws), b)) return r;
+  hipStream_t s = reinterpret_cast<hipStream_t>(st);
+  const bool conv = site_is_fwd(d->site) || site_is_dgrad(d->site);
+  if (conv) OPCK(launch_pack_conv(d->wt, d->co, d->ci, 3, 3, b.wf, b.wd, s));
+  else OPCK(launch_pack_convT(d->wt, d->ci, d->co, b.wf, b.wd, s));
+  if (b.b16)  // the planes of this GEMM's packed B
+    OPCK(launch_f2bf(site_is_fwd(d->site) || d->site == UNET_SITE_T_FWD ? b.wf : b.wd, b.b16, b.nw, s,
+                     const_cast<uint16_t*>(b.a.bl)));
+  const float* srcs[2] = {d->src0, d->src1};
+  for (int k = 0; k < 2; ++k)
+    if (b.s16[k]) OPCK(launch_f2bf(srcs[k], b.s16[k], b.ns[k], s));
+  if (b.y16) OPCK(launch_f2bf(d->yref, b.y16, b.ny, s));
+  if (b.a.e.stats) OPCK(hipMemsetAsync(b.a.e.stats, 0, sizeof(double) * kStatGroups * 2 * b.nstat, s));
+  if (b.a.e.bstats)
+    OPCK(hipMemsetAsync(b.a.e.bstats, 0, sizeof(double) * kStatGroups * 2 * std::min(b.a.e.n_split, b.a.N), s));
+  if (b.a.e.colsum1) OPCK(hipMemsetAsync(b.a.e.colsum1, 0, sizeof(double) * kStatGroups * b.ncs, s));
+  if (b.c.tile > 0 && b.c.split <= 1) {
+    // through launch_igemm, as the other per-op entry points run a forced tile
+    // (it alone admits the 8-channel chunks of the fused F(2x2) tiles)
+    const int knob = g_tune_igemm;
+    g_tune_igemm = b.c.tile;
+    const hipError_t e = launch_igemm(b.a, s);
+    g_tune_igemm = knob;
+    OPCK(e);
+    return 0;
+  }
+  if (b.c.tile > 0) {
+    OPCK(launch_igemm_v(b.a, s, b.c));
+    return 0;
+  }
+  const int knob = g_tune_igemm;
+  g_tune_igemm = -1;  // a knob that does not apply was dropped above
+  const hipError_t e = launch_igemm(b.a, s);
+  g_tune_igemm = knob;
+  OPCK(e);
+  return 0;
+}
+
+int unet_igemm_tile_table(int* out, int cap) {
+  const std::vector<IgemmTile>& v = igemm_tiles();
+  for (int i = 0; out && i < cap && i < (int)v.size(); ++i) {
+    const IgemmTile& t = v[i];
+    const int row[6] = {t.id, (int)t.family, t.bf16, t.x3, t.ksplit, t.wino_m};
+    std::copy(row, row + 6, out + 6 * i);
+  }
+  return (int)v.size();
 }
 
 }  // extern "C"

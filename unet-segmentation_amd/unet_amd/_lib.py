@@ -90,6 +90,10 @@ SIGNATURES = {
     "unet_conv1x1_ws_bytes": (_sz, [_i]),
     "unet_conv1x1_fwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "unet_conv1x1_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "unet_gemm_site_check": (_i, [_vp, ctypes.POINTER(_i)]),
+    "unet_gemm_site_ws_bytes": (_sz, [_vp]),
+    "unet_gemm_site_run": (_i, [_vp, _vp, _vp]),
+    "unet_igemm_tile_table": (_i, [ctypes.POINTER(_i), _i]),
     "unet_peak_probe": (_i, [_i, _i, ctypes.POINTER(ctypes.c_double), _vp]),
     "unet_tracker_create": (_vp, [_i, _i, ctypes.c_double, ctypes.c_double, _i]),
     "unet_tracker_destroy": (None, [_vp]),
@@ -134,6 +138,31 @@ SIGNATURES = {
     "unet_tuning_save": (_i, [ctypes.c_char_p]),
     "unet_tuning_load": (_i, [ctypes.c_char_p]),
 }
+
+class GemmSite(ctypes.Structure):
+    """unet_gemm_site of include/unet_hip.h (pass it with ctypes.byref)."""
+    _fields_ = ([(k, _i) for k in ("site", "n", "h", "w", "ci", "co", "c_split", "skip_h", "skip_w", "oy", "ox",
+                                   "n_split", "tile", "split")]
+                + [(k, _vp) for k in ("src0", "src1", "scale0", "shift0", "scale1", "shift1", "wt", "bias", "dst0",
+                                      "dst1", "yref", "bn_scale", "bn_shift", "bn_mean", "bn_invstd", "stats",
+                                      "bstats", "colsum1")])
+
+
+# UNET_SITE_* of include/unet_hip.h
+GEMM_SITES = ("F_PLAIN", "F_CAT", "F_EVAL", "D_POOL", "D_MASK", "D_SPLIT", "T_FWD", "T_MASK")
+# IgemmFamily of csrc/unet_internal.h, in order (column 1 of unet_igemm_tile_table)
+IGEMM_FAMILIES = ("Reg", "Halo", "Conv3Dma", "Ring", "Flat", "C64", "GemmRing", "Wino", "WinoFused")
+
+
+def igemm_tile_table():
+    """The rows of the igemm tile table: dicts of id, family, bf16, x3, ksplit, wino_m."""
+    lib = load()
+    n = lib.unet_igemm_tile_table(None, 0)
+    buf = (_i * (6 * n))()
+    lib.unet_igemm_tile_table(buf, n)
+    return [dict(id=buf[6 * k], family=IGEMM_FAMILIES[buf[6 * k + 1]], bf16=bool(buf[6 * k + 2]),
+                 x3=bool(buf[6 * k + 3]), ksplit=bool(buf[6 * k + 4]), wino_m=buf[6 * k + 5]) for k in range(n)]
+
 
 _lib = None
 _load_error = None
