@@ -543,6 +543,53 @@ int unet_ctc_frame_tables(const unet_ctc* c, int kind, int index, int32_t* host_
                           int32_t* host_res_labels, int64_t* host_res_areas, int64_t* host_pairs);
 int unet_ctc_stats(const unet_ctc* c, int64_t* host_out);
 
+/* Per-object measurements of a label stack (scripts/track.py:39-70
+ * get_mask_properties is an np.argwhere per label and frame): one record per
+ * object per frame, ordered by frame, then by ascending label (np.unique's
+ * order).  labels (n, h, w) uint16 on the device, 0 = background; image NULL
+ * or (n, h, w) uint8 on the device.
+ *   frame: index in the stack; label; area: pixels.
+ *   sum_y, sum_x, sum_yy, sum_xx, sum_xy: sums of the row index y, the column
+ *     index x and their products over the object's pixels.
+ *   min_y, min_x, max_y, max_x: inclusive extent (track.py:61-62).
+ *   boundary: pixels with a 4-neighbour that carries another label (background
+ *     included) or lies outside the frame.
+ *   edge: pixels in the first or last row or column.
+ *   contact: ordered 4-neighbour pairs (p, q), p in the object, q in a
+ *     different non-background object.
+ *   sum_v, sum_vv, min_v, max_v: sums of the intensity and its square, and its
+ *     extremes, over the object's pixels; all 0 without an image.
+ *   reserved fields are 0.
+ * Every field is an integer, so the records are bit-equal from run to run.
+ *   unet_region_props: frame_offsets (n + 1 int32, device): the records of
+ *     frame f are [frame_offsets[f], frame_offsets[f + 1]).  records: cap
+ *     records on the device (NULL with cap 0).  One host synchronisation,
+ *     after the index phase: *host_total (host, never NULL) receives the
+ *     object total; with total > cap the call returns -ENOSPC before it
+ *     touches records, frame_offsets valid.  ws >= unet_region_props_ws_bytes
+ *     (n x 16 KB + n x 4 B, each part rounded up to 256), 256-byte aligned.
+ *     Then two launches: the records' headers and neutral values, and one
+ *     accumulate launch over the whole stack (unet_region_props_launches
+ *     counts the latter; reset != 0 also zeroes the count).
+ *   unet_region_props_host: the same records from host arrays into host
+ *     arrays, in plain loops, no device call.
+ * -EINVAL before any device call (and a workspace size of 0) for n < 0, h or
+ * w < 1 or > 32768, h w > 2^30, cap < 0, n min(65535, h w) >= 2^31, a null or
+ * misaligned pointer: inside these limits no sum passes 63 bits.
+ * Tuning: "region_lds_objects" of unet_set_tuning. */
+typedef struct unet_region_record {
+  int32_t frame, label, area, boundary, edge, min_y, min_x, max_y, max_x, min_v, max_v, reserved0;
+  int64_t sum_y, sum_x, sum_yy, sum_xx, sum_xy, sum_v, sum_vv, contact, reserved1[2];
+} unet_region_record; /* 128 bytes */
+size_t unet_region_props_ws_bytes(int n, int h, int w);
+int unet_region_props(const uint16_t* labels, const uint8_t* image, int n, int h, int w, int32_t* frame_offsets,
+                      unet_region_record* records, long long cap, long long* host_total, void* ws,
+                      unet_stream_t stream);
+int unet_region_props_host(const uint16_t* host_labels, const uint8_t* host_image, int n, int h, int w,
+                           int32_t* host_frame_offsets, unet_region_record* host_records, long long cap,
+                           long long* host_total);
+long long unet_region_props_launches(int reset);
+
 /* Warping error and pixel error (Jain et al., "Boundary learning by
  * optimization with topological constraints", CVPR 2010; the measures the
  * U-Net paper ranks by; utils/metrics.py ends in a calculate_warping_error
@@ -723,6 +770,10 @@ int unet_split_instances(const uint8_t* mask, const uint8_t* markers, int n, int
  *  "ctc_dense_cells" largest (n_gt + 1)(n_res + 1) that unet_ctc_add_frames
  *                  counts in a dense LDS table (0..8192, 0 = every frame by
  *                  hash; -1 = the default, 4096).
+ *  "region_lds_objects" most objects of a frame that unet_region_props
+ *                  collects in its LDS table before the global atomics
+ *                  (0..512, 0 = every frame straight to global atomics; -1 =
+ *                  the default, 512; same records for every value).
  *  "split_threads" t (tests; 64..1024, a multiple of 64; -1 = the default,
  *                  1024): threads of unet_split_instances's growth workgroup
  *                  (same bits for every value). */

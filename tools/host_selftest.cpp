@@ -701,6 +701,60 @@ static void test_gemm_site() {
   }
 }
 
+// unet_region_props_host: exactly sized host buffers (the sanitizer sees any
+// access beside them), closed forms of two touching rectangles, -ENOSPC and
+// the argument checks
+static void test_region() {
+  const int n = 2, h = 6, w = 7;
+  std::vector<uint16_t> lab((size_t)n * h * w, 0);
+  std::vector<uint8_t> img(lab.size());
+  for (size_t i = 0; i < img.size(); ++i) img[i] = (uint8_t)(i * 37 + 11);
+  auto at = [&](int f, int y, int x) -> uint16_t& { return lab[((size_t)f * h + y) * w + x]; };
+  for (int y = 0; y < 3; ++y)
+    for (int x = 1; x < 6; ++x) at(0, y, x) = x < 3 ? 65535 : 7;  // 3 x 2 beside 3 x 3, sharing a side of 3
+  at(1, 5, 6) = 1;                                                 // one pixel in the last corner
+  std::vector<int32_t> off(n + 1, -1);
+  long long total = -1;
+  std::vector<unet_region_record> rec(3);
+  CHECK(unet_region_props_host(lab.data(), img.data(), n, h, w, off.data(), rec.data(), 2, &total) == -ENOSPC);
+  CHECK(total == 3 && off[0] == 0 && off[1] == 2 && off[2] == 3);
+  CHECK(unet_region_props_host(lab.data(), img.data(), n, h, w, off.data(), rec.data(), 3, &total) == 0);
+  CHECK(total == 3 && rec[0].label == 7 && rec[1].label == 65535 && rec[2].label == 1);
+  CHECK(rec[0].frame == 0 && rec[0].area == 9 && rec[0].contact == 3 && rec[1].contact == 3 && rec[1].area == 6);
+  CHECK(rec[0].min_y == 0 && rec[0].max_y == 2 && rec[0].min_x == 3 && rec[0].max_x == 5);
+  CHECK(rec[0].sum_y == 9 && rec[0].sum_x == 36 && rec[0].sum_yy == 15 && rec[0].sum_xx == 150 && rec[0].sum_xy == 36);
+  CHECK(rec[0].edge == 3 && rec[0].boundary == 8 && rec[1].boundary == 6);
+  long long sv = 0, svv = 0;
+  int lo = 255, hi = 0;
+  for (int y = 0; y < 3; ++y)
+    for (int x = 3; x < 6; ++x) {
+      const int v = img[(size_t)y * w + x];
+      sv += v, svv += v * v, lo = std::min(lo, v), hi = std::max(hi, v);
+    }
+  CHECK(rec[0].sum_v == sv && rec[0].sum_vv == svv && rec[0].min_v == lo && rec[0].max_v == hi);
+  CHECK(rec[2].frame == 1 && rec[2].area == 1 && rec[2].edge == 1 && rec[2].boundary == 1 && rec[2].contact == 0 &&
+        rec[2].min_y == 5 && rec[2].max_x == 6 && rec[2].sum_xy == 30);
+  CHECK(unet_region_props_host(lab.data(), nullptr, n, h, w, off.data(), rec.data(), 3, &total) == 0);
+  CHECK(rec[0].sum_v == 0 && rec[0].min_v == 0 && rec[0].max_v == 0 && rec[0].area == 9);
+  CHECK(unet_region_props_host(lab.data(), nullptr, 0, h, w, off.data(), nullptr, 0, &total) == 0 && total == 0 &&
+        off[0] == 0);
+  total = -1;
+  CHECK(unet_region_props_host(lab.data(), nullptr, 1, 32769, 1, off.data(), rec.data(), 3, &total) == -EINVAL);
+  CHECK(total == 0 && std::strstr(unet_last_error(), "32768") != nullptr);
+  CHECK(unet_region_props_host(lab.data(), nullptr, 1, 32768, 32769, off.data(), rec.data(), 3, &total) == -EINVAL);
+  CHECK(unet_region_props_host(lab.data(), nullptr, -1, h, w, off.data(), rec.data(), 3, &total) == -EINVAL);
+  CHECK(unet_region_props_host(nullptr, nullptr, n, h, w, off.data(), rec.data(), 3, &total) == -EINVAL);
+  // the device entry point rejects the same sizes before it touches the device
+  void* dummy = reinterpret_cast<void*>(uintptr_t{4096});
+  CHECK(unet_region_props(lab.data(), nullptr, 1, 1, 32769, off.data(), rec.data(), 3, &total, dummy, nullptr) == -EINVAL);
+  CHECK(unet_region_props(lab.data(), nullptr, -1, h, w, off.data(), rec.data(), 3, &total, dummy, nullptr) == -EINVAL);
+  CHECK(unet_region_props(lab.data(), nullptr, n, h, w, off.data(), rec.data(), 3, nullptr, dummy, nullptr) == -EINVAL);
+  CHECK(unet_region_props_ws_bytes(1, 32769, 1) == 0 && unet_region_props_ws_bytes(3, 5, 7) == 2 * 3 * 8192 + 256);
+  CHECK(unet_set_tuning("region_lds_objects", -2) == -EINVAL && unet_set_tuning("region_lds_objects", 2) == 0 &&
+        unet_set_tuning("region_lds_objects", -1) == 0);
+  CHECK(unet_region_props_launches(1) >= 0 && unet_region_props_launches(0) == 0);
+}
+
 int main(int argc, char** argv) {
   test_plans();
   test_gemm_site();
@@ -708,6 +762,7 @@ int main(int argc, char** argv) {
   test_tracker();
   test_ctc();
   test_warp();
+  test_region();
   test_misc();
   if (argc > 1) test_selection(argv[1], argc > 2 && std::strcmp(argv[2], "--record") == 0);
   else CHECK(!"usage: host_selftest tests/golden/gemm_selection.txt [--record]");
