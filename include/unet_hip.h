@@ -430,6 +430,14 @@ int unet_rand_index(const uint16_t* gt, const uint16_t* pred, int h, int w, doub
  *     which a 16-bit mask cannot carry); -EIO for a HIP error.  n = 0: 0.
  *   unet_tracker_relabel_launches: relabel kernel launches of this process
  *     so far (reset != 0 clears the count after reading it).
+ *   unet_tracker_load_result (host only): gives a tracker that was given no
+ *     frame the tracks and frame maps of another linker (unet_link_assemble):
+ *     rows (n_rows x 4: id, start, end, parent; row q carries id q + 1, parent
+ *     -1 = root), frames (n_frames numbers, strictly ascending), and for frame
+ *     f the ascending labels[map_offsets[f] .. map_offsets[f + 1]) with their
+ *     track ids (0 = none).  Afterwards unet_tracker_tracks, _frame_map and
+ *     _relabel serve the loaded result.  -EBUSY for a tracker that already has
+ *     frames, -EINVAL for anything else that does not hold.
  * unet_linear_sum_assignment: scipy.optimize.linear_sum_assignment's
  *   minimisation on a row-major nr x nc fp64 cost matrix (host pointers,
  *   min(nr, nc) pairs sorted by row); -EINVAL for NaN / -inf / infeasible. */
@@ -451,6 +459,9 @@ size_t unet_tracker_relabel_ws_bytes(int t, int h, int w);
 int unet_tracker_relabel(unet_tracker* t, const uint16_t* labels, const int32_t* host_frames, int n, uint16_t* out,
                          void* ws, unet_stream_t stream);
 long long unet_tracker_relabel_launches(int reset);
+int unet_tracker_load_result(unet_tracker* t, const int32_t* host_rows, int n_rows, const int32_t* host_frames,
+                             int n_frames, const int32_t* host_map_offsets, const int32_t* host_labels,
+                             const int32_t* host_ids);
 int unet_linear_sum_assignment(long long nr, long long nc, const double* host_cost, int64_t* host_row_ind,
                                int64_t* host_col_ind);
 
@@ -589,6 +600,75 @@ int unet_region_props_host(const uint16_t* host_labels, const uint8_t* host_imag
                            int32_t* host_frame_offsets, unet_region_record* host_records, long long cap,
                            long long* host_total);
 long long unet_region_props_launches(int reset);
+
+/* Distance-based linker ("Distance-based linker", has the
+ * definitions): the objects of consecutive frames of a region table are
+ * assigned to each other by the squared distance of their quantised centroids.
+ *   Quantised centroid, 1/16 pixel: qy = floor((32 sum_y + area) / (2 area)),
+ *     qx likewise.  d(i, j) = dqy^2 + dqx^2 in int64.  gate_q = round(16 gate),
+ *     g2 = gate_q^2; a pair is permitted iff d <= g2.
+ *   Pair f = frames (f, f + 1) of the table, P previous and C current objects
+ *     in ascending label order: a P x (C + P) assignment problem, entry
+ *     (i, j < C) = d(i, j) where permitted, entry (i, C + i) = g2 (row i's
+ *     private "no successor" column), every other entry absent; every row
+ *     assigned, least total.  Solved by shortest augmenting paths (Crouse 2016)
+ *     with rows in ascending order, int64 duals, the strict update r <
+ *     shortest[j], and the next column taken among the unscanned columns of
+ *     least distance (a) unassigned before assigned, (b) lowest index -- the
+ *     algorithm is part of the definition, since the optimum need not be unique.
+ *   unet_link_frames: records / frame_offsets (n + 1) as unet_region_props
+ *     leaves them on the device, total = frame_offsets[n] (the host_total of
+ *     that call).  Outputs on the device, indexed by record: prev[r] = the
+ *     record of the linked predecessor of current object r or -1 (frame 0: all
+ *     -1); dist[r] = that link's d or -1; mother[r], for a current object
+ *     without predecessor (a birth) and division_gate_q > 0 = the record of the
+ *     previous object i with the least d(i, r) <= division_gate_q^2 among those
+ *     that have a linked successor (ties to the lowest i), else -1;
+ *     pair_total[f] (max(n - 1, 0) int64) = the optimal total of pair f.
+ *     One launch for the whole sequence, one workgroup of 256 lanes per frame
+ *     pair (unet_link_launches counts the launches of this process; reset != 0
+ *     also zeroes the count); no host synchronisation.  A workgroup computes
+ *     the centroids of its two frames in its prologue and keeps them with the
+ *     duals, shortest, path, col4row, row4col and the scanned flags in LDS
+ *     (33 bytes per object + 12 per previous object) where P + C is at most
+ *     "link_lds_objects" of unet_set_tuning, in ws otherwise -- the same code
+ *     and the same bytes.  The cost matrix is never stored.
+ *     ws >= unet_link_ws_bytes(n, total), 256-byte aligned: nine arrays of
+ *     16, 16, 8, 8, 8, 4, 8, 8 and 2 bytes x total, each rounded up to 256;
+ *     0 for n < 2 or total = 0 (ws may then be NULL).
+ *     n = 0 launches nothing; n = 1 only fills frame 0; frames without objects
+ *     are valid.
+ *   unet_link_frames_host: the same outputs from host records into host
+ *     arrays: plain loops over the explicit matrix, no device call.
+ *   unet_link_assemble (host only): chains the links into tracks.  frames: the
+ *     n frame numbers, strictly ascending.  Frames in order, objects in
+ *     ascending label order: a previous object i with successor k and claimants
+ *     {j : mother[j] = i} divides when max_children >= 2 and a claimant passes
+ *     min(area_k, area_j) / max(area_k, area_j) >= division_min_ratio; of the
+ *     passing claimants up to max_children - 1 are taken, nearest first, ties
+ *     to the lowest label; then k and the taken claimants start tracks whose
+ *     parent is i's track, which ends in the previous frame.  Every other birth
+ *     starts a root track, every other linked object extends its predecessor's.
+ *     Ids are 1, 2, ... in that order.  rows: up to rows_cap rows (id, start,
+ *     end, parent; -1 = root), total rows at most; ids: the track id of every
+ *     record (with frame_offsets and the records' labels these are the
+ *     per-frame label -> track maps).  Returns the number of tracks.
+ *   -EINVAL before any device call: n < 0, total < 0 or >= 2^30, gate_q outside
+ *   [1, 65535], division_gate_q outside [0, 65535], a null or misaligned
+ *   pointer (frame_offsets, prev, mother 4 bytes; dist, pair_total 8; records
+ *   16; ws 256), frame numbers that do not ascend strictly (assemble). */
+size_t unet_link_ws_bytes(int n, long long total);
+int unet_link_frames(const unet_region_record* records, const int32_t* frame_offsets, int n, long long total,
+                     int gate_q, int division_gate_q, int32_t* prev, int64_t* dist, int32_t* mother,
+                     int64_t* pair_total, void* ws, unet_stream_t stream);
+int unet_link_frames_host(const unet_region_record* host_records, const int32_t* host_frame_offsets, int n,
+                          long long total, int gate_q, int division_gate_q, int32_t* host_prev, int64_t* host_dist,
+                          int32_t* host_mother, int64_t* host_pair_total);
+long long unet_link_launches(int reset);
+int unet_link_assemble(const unet_region_record* host_records, const int32_t* host_frame_offsets, int n,
+                       const int32_t* host_frames, const int32_t* host_prev, const int64_t* host_dist,
+                       const int32_t* host_mother, double division_min_ratio, int max_children, int32_t* host_rows,
+                       int rows_cap, int32_t* host_ids);
 
 /* Warping error and pixel error (Jain et al., "Boundary learning by
  * optimization with topological constraints", CVPR 2010; the measures the
@@ -774,6 +854,10 @@ int unet_split_instances(const uint8_t* mask, const uint8_t* markers, int n, int
  *                  collects in its LDS table before the global atomics
  *                  (0..512, 0 = every frame straight to global atomics; -1 =
  *                  the default, 512; same records for every value).
+ *  "link_lds_objects" most objects P + C of a frame pair that unet_link_frames
+ *                  serves from LDS (0..3600, 0 = every pair from the workspace;
+ *                  -1 = the default, 3600: what 160 KB hold; same bytes for
+ *                  every value).
  *  "split_threads" t (tests; 64..1024, a multiple of 64; -1 = the default,
  *                  1024): threads of unet_split_instances's growth workgroup
  *                  (same bits for every value). */

@@ -755,6 +755,111 @@ static void test_region() {
   CHECK(unet_region_props_launches(1) >= 0 && unet_region_props_launches(0) == 0);
 }
 
+// unet_link_frames_host / unet_link_assemble / unet_tracker_load_result on
+// exactly sized host buffers: a tie (two predecessors equidistant from one
+// successor), the gate's boundary, empty frames, a division, and the argument
+// checks.  Records with area 16 and sum = q have the quantised centroid q.
+static unet_region_record link_rec(int frame, int label, int qy, int qx, int area = 16) {
+  unet_region_record r;
+  std::memset(&r, 0, sizeof r);
+  r.frame = frame, r.label = label, r.area = area;
+  r.sum_y = (int64_t)qy * area / 16, r.sum_x = (int64_t)qx * area / 16;
+  return r;
+}
+
+static void test_link() {
+  {  // the tie: row 1's search reaches row 0's private column first (lowest index), so row 0 gives way
+    std::vector<unet_region_record> rec = {link_rec(0, 1, 80, 32), link_rec(0, 2, 80, 128), link_rec(1, 1, 80, 80)};
+    const int32_t off[3] = {0, 2, 3};
+    std::vector<int32_t> prev(3, 9), mother(3, 9);
+    std::vector<int64_t> dist(3, 9), total(1, 9);
+    CHECK(unet_link_frames_host(rec.data(), off, 2, 3, 160, 0, prev.data(), dist.data(), mother.data(),
+                                total.data()) == 0);
+    CHECK(prev[0] == -1 && prev[1] == -1 && prev[2] == 1 && dist[2] == 48 * 48 && mother[2] == -1);
+    CHECK(total[0] == 48 * 48 + 160 * 160);
+    // on the gate and one past it
+    rec = {link_rec(0, 1, 0, 0), link_rec(1, 1, 0, 47)};
+    const int32_t off2[3] = {0, 1, 2};
+    CHECK(unet_link_frames_host(rec.data(), off2, 2, 2, 47, 0, prev.data(), dist.data(), mother.data(),
+                                total.data()) == 0 && prev[1] == 0 && dist[1] == 47 * 47 && total[0] == 47 * 47);
+    rec[1] = link_rec(1, 1, 1, 47);
+    CHECK(unet_link_frames_host(rec.data(), off2, 2, 2, 47, 0, prev.data(), dist.data(), mother.data(),
+                                total.data()) == 0 && prev[1] == -1 && dist[1] == -1 && total[0] == 47 * 47);
+    CHECK(unet_link_frames_host(rec.data(), off2, 2, 2, 0, 0, prev.data(), dist.data(), mother.data(),
+                                total.data()) == -EINVAL);
+    CHECK(unet_link_frames_host(rec.data(), off2, 2, 2, 47, 65536, prev.data(), dist.data(), mother.data(),
+                                total.data()) == -EINVAL);
+    CHECK(unet_link_frames_host(nullptr, off2, 2, 2, 47, 0, prev.data(), dist.data(), mother.data(),
+                                total.data()) == -EINVAL);
+    // the device entry point rejects the same before it touches the device
+    void* dummy = reinterpret_cast<void*>(uintptr_t{4096});
+    CHECK(unet_link_frames(rec.data(), off2, -1, 2, 47, 0, prev.data(), dist.data(), mother.data(), total.data(), dummy,
+                           nullptr) == -EINVAL);
+    CHECK(unet_link_frames(rec.data(), off2, 2, 2, 47, 0, prev.data(), dist.data(), mother.data(), total.data(),
+                           nullptr, nullptr) == -EINVAL);
+    CHECK(unet_link_frames(rec.data(), off2, 2, 2, 65536, 0, prev.data(), dist.data(), mother.data(), total.data(),
+                           dummy, nullptr) == -EINVAL);
+    CHECK(unet_link_frames(nullptr, nullptr, 0, 0, 47, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == 0);
+    CHECK(unet_link_ws_bytes(1, 5) == 0 && unet_link_ws_bytes(2, 0) == 0 && unet_link_ws_bytes(2, 5) == 9 * 256);
+    CHECK(unet_set_tuning("link_lds_objects", -2) == -EINVAL && unet_set_tuning("link_lds_objects", 0) == 0 &&
+          unet_set_tuning("link_lds_objects", -1) == 0);
+    CHECK(unet_link_launches(1) >= 0 && unet_link_launches(0) == 0);
+  }
+  {  // empty frames around two objects; no frame at all
+    std::vector<unet_region_record> rec = {link_rec(1, 3, 0, 0), link_rec(1, 9, 0, 16), link_rec(3, 5, 0, 0)};
+    const int32_t off[5] = {0, 0, 2, 2, 3}, frames[4] = {2, 4, 6, 8};
+    std::vector<int32_t> prev(3, 9), mother(3, 9), rows(12, 9), ids(3, 9);
+    std::vector<int64_t> dist(3, 9), total(3, 9);
+    CHECK(unet_link_frames_host(rec.data(), off, 4, 3, 320, 320, prev.data(), dist.data(), mother.data(),
+                                total.data()) == 0);
+    CHECK(prev[0] == -1 && prev[1] == -1 && prev[2] == -1 && mother[2] == -1);
+    CHECK(total[0] == 0 && total[1] == 2 * 320 * 320 && total[2] == 0);
+    CHECK(unet_link_assemble(rec.data(), off, 4, frames, prev.data(), dist.data(), mother.data(), 0.5, 2, rows.data(),
+                             3, ids.data()) == 3);
+    CHECK(rows[0] == 1 && rows[1] == 4 && rows[2] == 4 && rows[3] == -1 && rows[8] == 3 && rows[9] == 8);
+    CHECK(ids[0] == 1 && ids[1] == 2 && ids[2] == 3);
+    CHECK(unet_link_frames_host(nullptr, nullptr, 0, 0, 16, 0, nullptr, nullptr, nullptr, nullptr) == 0);
+    CHECK(unet_link_assemble(nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0.5, 2, nullptr, 0, nullptr) == 0);
+    const int32_t same[4] = {2, 4, 4, 8};
+    CHECK(unet_link_assemble(rec.data(), off, 4, same, prev.data(), dist.data(), mother.data(), 0.5, 2, rows.data(), 3,
+                             ids.data()) == -EINVAL);
+  }
+  {  // a division: the mother's successor and the nearest claimant that passes the area ratio become daughters
+    std::vector<unet_region_record> rec = {link_rec(0, 1, 160, 160, 32), link_rec(1, 1, 160, 176),
+                                           link_rec(1, 2, 192, 160, 4), link_rec(1, 3, 160, 112)};
+    const int32_t off[3] = {0, 1, 4}, frames[2] = {3, 5};
+    std::vector<int32_t> prev(4, 9), mother(4, 9), rows(16, 9), ids(4, 9);
+    std::vector<int64_t> dist(4, 9), total(1, 9);
+    CHECK(unet_link_frames_host(rec.data(), off, 2, 4, 24, 96, prev.data(), dist.data(), mother.data(),
+                                total.data()) == 0);
+    CHECK(prev[1] == 0 && prev[2] == -1 && prev[3] == -1 && mother[1] == -1 && mother[2] == 0 && mother[3] == 0);
+    CHECK(unet_link_assemble(rec.data(), off, 2, frames, prev.data(), dist.data(), mother.data(), 0.5, 2, rows.data(),
+                             4, ids.data()) == 4);
+    CHECK(rows[0] == 1 && rows[1] == 3 && rows[2] == 3 && rows[3] == -1);   // the mother ends in frame 3
+    CHECK(ids[1] == 2 && rows[7] == 1 && ids[2] == 3 && rows[11] == -1 && ids[3] == 4 && rows[15] == 1);
+    // rows_cap below the count: the count still comes back, nothing is written past the cap
+    std::vector<int32_t> two(8, 9);
+    CHECK(unet_link_assemble(rec.data(), off, 2, frames, prev.data(), dist.data(), mother.data(), 0.5, 2, two.data(), 2,
+                             ids.data()) == 4 && two[4] == 2);
+    unet_tracker* t = unet_tracker_create(8, 8, 0.3, 0.1, 2);
+    const int32_t labels[4] = {1, 1, 2, 3};
+    const int32_t bad_frames[2] = {5, 3};
+    CHECK(unet_tracker_load_result(t, rows.data(), 4, bad_frames, 2, off, labels, ids.data()) == -EINVAL);
+    CHECK(unet_tracker_num_frames(t) == 0 && unet_tracker_num_tracks(t) == 0);
+    CHECK(unet_tracker_load_result(t, rows.data(), 4, frames, 2, off, labels, ids.data()) == 0);
+    CHECK(unet_tracker_num_frames(t) == 2 && unet_tracker_num_tracks(t) == 4);
+    std::vector<int32_t> back(16, 9), lab(3), got(3);
+    int32_t fr = -1;
+    CHECK(unet_tracker_tracks(t, back.data(), 4) == 4 && back == rows);
+    CHECK(unet_tracker_frame_map(t, 1, &fr, lab.data(), got.data(), 3) == 3 && fr == 5 && lab[2] == 3 && got[2] == 4);
+    CHECK(unet_tracker_load_result(t, rows.data(), 4, frames, 2, off, labels, ids.data()) == -EBUSY);
+    unet_tracker_destroy(t);
+    t = unet_tracker_create(8, 8, 0.3, 0.1, 2);
+    CHECK(unet_tracker_load_result(t, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr) == 0);
+    unet_tracker_destroy(t);
+  }
+}
+
 int main(int argc, char** argv) {
   test_plans();
   test_gemm_site();
@@ -763,6 +868,7 @@ int main(int argc, char** argv) {
   test_ctc();
   test_warp();
   test_region();
+  test_link();
   test_misc();
   if (argc > 1) test_selection(argv[1], argc > 2 && std::strcmp(argv[2], "--record") == 0);
   else CHECK(!"usage: host_selftest tests/golden/gemm_selection.txt [--record]");

@@ -14,7 +14,7 @@ using namespace unet;
 namespace unet {
 extern int g_tune_igemm, g_tune_wgrad, g_autotune, g_force_split, g_force_tile, g_concurrent, g_wino_max,
     g_wino_dgrad_max, g_wino_wgrad_max, g_bf16_norm, g_bn_fold, g_wino4_fwd_min_cg, g_wino4_fwd_small_cg,
-    g_maxpool_vec8, g_wgrad_fwd_u, g_ctc_chunk_frames, g_ctc_dense_cells, g_region_lds_objects;
+    g_maxpool_vec8, g_wgrad_fwd_u, g_ctc_chunk_frames, g_ctc_dense_cells, g_region_lds_objects, g_link_lds_objects;
 hipError_t launch_fill(float* p, size_t n, float v, hipStream_t s);
 hipError_t launch_pair_sum(const double* st, int g, int c, float* out, hipStream_t s);
 }  // namespace unet
@@ -639,6 +639,10 @@ int unet_set_tuning(const char* key, int value) {
   else if (k == "region_lds_objects") {  // region.hip clamps it to its table; -1 = the default
     if (value < -1) return -EINVAL;
     g_region_lds_objects = value;
+  }
+  else if (k == "link_lds_objects") {  // link.hip clamps it to what a CU's LDS holds; -1 = the default
+    if (value < -1) return -EINVAL;
+    g_link_lds_objects = value;
   }
   else if (k == "split_threads") {  // split.hip: the growth workgroup's size, -1 = the default
     if (value != -1 && (value < 64 || value > 1024 || value % 64)) return -EINVAL;

@@ -628,4 +628,45 @@ long long unet_tracker_relabel_launches(int reset) {
   return reset ? g_relabel_launches.exchange(0) : g_relabel_launches.load();
 }
 
+int unet_tracker_load_result(unet_tracker* t, const int32_t* rows, int n_rows, const int32_t* frames, int n_frames,
+                             const int32_t* map_offsets, const int32_t* labels, const int32_t* ids) {
+  if (!t || n_rows < 0 || n_frames < 0 || (n_rows > 0 && !rows) || (n_frames > 0 && (!frames || !map_offsets))) {
+    unet::set_last_error("unet_tracker_load_result: null tracker / rows / frames / map_offsets or a negative count");
+    return -EINVAL;
+  }
+  if (!t->maps.empty() || !t->first) return -EBUSY;
+  for (int q = 0; q < n_rows; ++q)
+    if (rows[4 * q] != q + 1 || rows[4 * q + 3] == 0 || rows[4 * q + 3] > n_rows) {
+      unet::set_last_error("unet_tracker_load_result: row " + std::to_string(q) + " must carry track id " +
+                           std::to_string(q + 1) + " and a parent of -1 or another row's id");
+      return -EINVAL;
+    }
+  for (int f = 0; f < n_frames; ++f) {
+    if ((f > 0 && frames[f] <= frames[f - 1]) || map_offsets[f] < 0 || map_offsets[f + 1] < map_offsets[f] ||
+        (map_offsets[f + 1] > map_offsets[f] && (!labels || !ids))) {
+      unet::set_last_error("unet_tracker_load_result: frame numbers must ascend strictly and map_offsets ascend");
+      return -EINVAL;
+    }
+    for (int k = map_offsets[f]; k < map_offsets[f + 1]; ++k)
+      if (labels[k] <= 0 || labels[k] >= kLabels || (k > map_offsets[f] && labels[k] <= labels[k - 1]) || ids[k] < 0 ||
+          ids[k] > n_rows) {
+        unet::set_last_error("unet_tracker_load_result: frame " + std::to_string(frames[f]) +
+                             " needs ascending labels in [1, 65535] and track ids in [0, n_rows]");
+        return -EINVAL;
+      }
+  }
+  t->tracks.reserve((size_t)n_rows);
+  for (int q = 0; q < n_rows; ++q)
+    t->tracks.push_back({rows[4 * q], rows[4 * q + 1], rows[4 * q + 2], rows[4 * q + 3] < 0 ? -1 : rows[4 * q + 3]});
+  for (int f = 0; f < n_frames; ++f) {
+    unet_tracker::FrameMap m;
+    m.frame = frames[f];
+    m.labels.assign(labels + map_offsets[f], labels + map_offsets[f + 1]);
+    m.ids.assign(ids + map_offsets[f], ids + map_offsets[f + 1]);
+    t->map_of_frame[m.frame] = (int)t->maps.size();
+    t->maps.push_back(std::move(m));
+  }
+  return 0;
+}
+
 }  // extern "C"

@@ -125,6 +125,12 @@ SIGNATURES = {
     "unet_region_props": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp]),
     "unet_region_props_host": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, ctypes.c_longlong, _vp]),
     "unet_region_props_launches": (ctypes.c_longlong, [_i]),
+    "unet_link_ws_bytes": (_sz, [_i, ctypes.c_longlong]),
+    "unet_link_frames": (_i, [_vp, _vp, _i, ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "unet_link_frames_host": (_i, [_vp, _vp, _i, ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp]),
+    "unet_link_launches": (ctypes.c_longlong, [_i]),
+    "unet_link_assemble": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_double, _i, _vp, _i, _vp]),
+    "unet_tracker_load_result": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "unet_warping_error_ws_bytes": (_sz, [_i, _i, _i]),
     "unet_warping_error": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "unet_simple_point_table": (None, [_vp]),
@@ -224,7 +230,7 @@ def stream_of(device=None):
 _HASHED = ["igemm.hip", "igemm_bf16.hip", "conv3_dma.hip", "conv3_ring.hip", "winograd.hip", "elementwise.hip", "elastic.hip",
            "tiling.hip", "weightmap.hip", "postproc.hip", "track.hip", "ops.hip", "plan.hip", "wgrad3_ring.hip",
            "conv3_ring_pt.hip", "peak.hip", "gemm_ring.hip", "wgradT_ring.hip", "conv3_flat.hip", "conv3_c64.hip", "gemm_ring_p1.hip",
-           "gemm_ring_p2.hip", "wgrad_plane.hip", "igemm_plane.hip", "ctc.hip", "warp.hip", "split.hip", "predict.hip", "region.hip", "unet_internal.h", "gemm_common.h", "ring_common.h", "conv3_ring_kernel.h",
+           "gemm_ring_p2.hip", "wgrad_plane.hip", "igemm_plane.hip", "ctc.hip", "warp.hip", "split.hip", "predict.hip", "region.hip", "link.hip", "unet_internal.h", "gemm_common.h", "ring_common.h", "conv3_ring_kernel.h",
            os.path.join("..", "..", "include", "unet_hip.h")]
 
 

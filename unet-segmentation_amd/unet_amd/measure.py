@@ -124,12 +124,13 @@ def _device_stack(x, what):
     return x
 
 
-def region_props(labels, image=None, cap=None) -> RegionTable:
+def region_props(labels, image=None, cap=None, keep_device=False) -> RegionTable:
     """labels (n, h, w) integer labels on the HIP device (0 = background, uint16
     or any integer dtype within [0, 65535]); image None or (n, h, w) uint8 on
     the same device.  cap: records to provide for on the first try (default: a
     guess of 256 per frame); if the stack holds more the call is repeated once
-    with the exact total."""
+    with the exact total.  keep_device: return (table, the device buffer of the
+    records, the device frame offsets) for a kernel that reads them in place."""
     import torch
     from .postproc import _u16
     lab = _device_stack(labels, "region_props")
@@ -166,7 +167,8 @@ def region_props(labels, image=None, cap=None) -> RegionTable:
         cap = int(total.value)
     _lib.check(rc, "unet_region_props")
     records = rec[:int(total.value)].cpu().numpy().reshape(-1).view(RECORD).copy()
-    return RegionTable(records, offsets.cpu().numpy(), (n, h, w), img is not None)
+    table = RegionTable(records, offsets.cpu().numpy(), (n, h, w), img is not None)
+    return (table, rec, offsets) if keep_device else table
 
 
 def _host_u16(labels, what):
